@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py - images/sec of the SCD embedding-and-naming hot path on MI355X.
 
-  python bench.py --gpus N --steps K --warmup W [--config c2|c4]
+  python bench.py --gpus N --steps K --warmup W [--config c2|c4] [--full] [--dump-outputs DIR]
   N > 1: one rank per GPU.  Launched by the driver through torch.distributed.run (WORLD_SIZE = N in the environment); started
   bare (`python bench.py --gpus N`), it spawns that launcher itself as a child process BEFORE touching the GPU.
 
@@ -12,8 +12,14 @@ one step = CLIP ViT-B/16 encode + L2-norm -> full-vocab similarity + top-k -> se
 convergence (topk/num_common_vote/num_common_linear = 3/10/2, scripts/evaluate_unsupervised.sh).
 Weak scaling: per-GPU images are fixed; `value` = images of all ranks / max-over-ranks step time.
 
-Prints ONE JSON line (rank 0) with `roofline` (dominant kernel: the fc1 GEMM of the ViT blocks, MFMA-bound,
-timed live with HIP events) and `cpu_baseline` (the oracle timed on the host cores on a bounded sample).
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the K steps and prints the headline (`value`, `ms_per_step`)
+with the synthetic run's quality (`vote_iters`, `synthetic_name_accuracy`): nothing else is measured in or after the timed steps.
+`--full` adds everything else: per-stage times, `roofline` (dominant kernel: the fc1 GEMM of the ViT blocks, MFMA-bound, timed live
+with HIP events), board power, `secondary_rooflines` (runs of their own after the timed region) and `cpu_baseline` (the oracle timed
+on the host cores on a bounded sample; `--no-cpu-baseline` leaves it out).
+`--dump-outputs DIR`: after the timed steps, rank 0 writes what its last step returned as DIR/<name>.npy (float32 / float64; matrices
+larger than DUMP_MAX_ELEMS as a fixed seeded sample of rows, the row numbers in DIR/<name>_rows.npy).  The inputs are seeded: with
+the same arguments two builds can be compared output for output.
 """
 import argparse
 import json
@@ -69,12 +75,18 @@ def parse():
     # the ramp-up / tail of the ~60 launches per batch: +1.5-1.9 % over 665 on the same box, features bit-identical (tools/bigbatch_check.py)
     p.add_argument("--batch", type=int, default=3990)
     p.add_argument("--vocab", type=int, default=None, help="names in the vocabulary (default = the config's: 21,000; c1 1,000; c5 100,000)")
-    p.add_argument("--no-cpu-baseline", action="store_true")
+    p.add_argument("--full", action="store_true",
+                   help="also measure what the headline does not need: stage times, rooflines, board power, cpu_baseline")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write the last timed step's outputs as DIR/<name>.npy (rank 0)")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out cpu_baseline")
     p.add_argument("--cpu-baseline-only", action="store_true", help="print the cpu_baseline object and exit (no GPU work; how the main run obtains it)")
     p.add_argument("--cluster", choices=["SSKM", "KM"], default="SSKM",
                    help="clustering stage: SSKM (semi-supervised K-Means, the north-star path; default) or KM = the flag of the shipped "
                         "scripts/evaluate_unsupervised.sh, `KMeans(n_clusters, random_state=0).fit(u_feats)` (main_unsup.py:362)")
     a = p.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        p.error("--steps must be >= 1 and --warmup >= 0")
     if a.cluster == "KM" and a.gpus > 1:
         p.error("--cluster KM is a single-process fit (as in the reference, main_unsup.py:362): use --gpus 1")
     if a.config == "c5" and a.cluster != "SSKM":
@@ -106,6 +118,17 @@ def spawn_ranks(n):
     return subprocess.run(cmd, env=env).returncode
 
 
+def usable_cpus():
+    """CPUs this process may use: the affinity mask, capped by OMP_NUM_THREADS when it is set (a container's CPU quota does not show in
+    os.cpu_count(), and a thread sweep sized by the host's count oversubscribes it)."""
+    n = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
+    try:
+        n = min(n, int(os.environ.get("OMP_NUM_THREADS", "")))
+    except ValueError:
+        pass
+    return max(1, n)
+
+
 def cpu_baseline(seed=0):
     """The oracle ('port') timed on the host cores on a bounded sample of the same workload, one leg per stage of SURVEY.md 8(d)
     (an end-to-end CPU pass over 127k images would take hours); `value` composes the stages of the metric harmonically.
@@ -117,7 +140,7 @@ def cpu_baseline(seed=0):
     from oracle import clip_oracle as co
     from oracle import naming_oracle as no
     from scd_amd.clip import weights as W
-    cores = os.cpu_count() or 1
+    cores = usable_cpus()
     sweep = sorted({min(cores, t) for t in (32, 64, 128, cores)})
     t_budget = time.time()
     used = {}
@@ -482,9 +505,48 @@ def cpu_baseline_child():
         return {"error": "%s: %s" % (type(e).__name__, e)}
 
 
+DUMP_MAX_ELEMS = 1 << 20        # per array; a larger matrix is written as a fixed seeded sample of its rows
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(path, out, keys, nouns):
+    """What the last timed step returned, as path/<name>.npy: the arrays `keys` of `out`, the candidate names as vocabulary rows
+    (`cand_name_idx`, -1 for a name not in `nouns`), the final centres and the vote iterations.  Integers as float64 (exact), floats as
+    float32.  A matrix of more than DUMP_MAX_ELEMS elements keeps the rows of RandomState(0).choice (sorted), written as <name>_rows.npy:
+    the same rows on every run of the same shape.  Raises if the files would exceed DUMP_MAX_BYTES."""
+    arrays = []
+    for k in keys:
+        x = out[k]
+        rows = None
+        size = int(np.prod(x.shape))
+        if x.ndim >= 1 and size > DUMP_MAX_ELEMS:
+            n = int(x.shape[0])
+            rows = np.sort(np.random.RandomState(0).choice(n, max(1, DUMP_MAX_ELEMS // (size // n)), replace=False))
+            x = x[torch.as_tensor(rows, device=x.device)] if torch.is_tensor(x) else x[rows]
+        if torch.is_tensor(x):
+            x = x.detach()
+            x = (x.float() if x.is_floating_point() and x.dtype != torch.float64 else x).cpu().numpy()
+        arrays.append((k, np.asarray(x)))
+        if rows is not None:
+            arrays.append((k + "_rows", rows))
+    row_of = {nm: i for i, nm in enumerate(nouns)}
+    arrays.append(("cand_name_idx", np.array([row_of.get(nm, -1) for nm in out["cand_names"]])))
+    cc = getattr(out["kmeans"], "cluster_centers_", None)
+    if cc is not None:
+        arrays.append(("cluster_centers", cc.detach().float().cpu().numpy() if torch.is_tensor(cc) else np.asarray(cc)))
+    arrays.append(("vote_iters", np.array([out["vote_iters"]])))
+    arrays = [(k, a.astype(np.float32 if a.dtype.kind == "f" and a.dtype != np.float64 else np.float64)) for k, a in arrays]
+    total = sum(a.nbytes for _, a in arrays)
+    if total > DUMP_MAX_BYTES:
+        raise RuntimeError("--dump-outputs: %d bytes over the %d-byte limit" % (total, DUMP_MAX_BYTES))
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrays:
+        np.save(os.path.join(path, k + ".npy"), a)
+
+
 def main_c1(args, dev):
-    """BASELINE configs[0]: the cached-feature path (no encoder).  One JSON line; `roofline` is the E-step call of the fit's shape (the
-    path's HBM-bound kernel), `secondary_rooflines` carries the fit itself - the step is launch- and latency-bound, and says so."""
+    """BASELINE configs[0]: the cached-feature path (no encoder).  One JSON line; with --full its `roofline` is the E-step call of the fit's
+    shape (the path's HBM-bound kernel), `km_fit` carries the fit itself - the step is launch- and latency-bound, and says so."""
     from scd_amd import ops, pipeline
     n, k, v = args.images, args.n_cluster, args.vocab
     g = torch.Generator(device=dev).manual_seed(2024)
@@ -504,19 +566,21 @@ def main_c1(args, dev):
     stage_ms = {}
 
     def step(timed):
-        timers = [] if timed else None
+        timers = [] if (timed and args.full) else None
         out = pipeline.run_cached(xf, cf, mask_lab, wt, nouns, k, topk=3, num_common_vote=10, num_common_linear=2, timers=timers,
                                   cluster=args.cluster, l_targets=l_targets)
         if timed:
             torch.cuda.synchronize()
+        if timers:
             for (n0, e0), (n1, e1) in zip(timers[:-1], timers[1:]):
                 stage_ms[n1] = stage_ms.get(n1, 0.0) + e0.elapsed_time(e1)
         return out
     for _ in range(args.warmup):
         out = step(False)
     torch.cuda.synchronize()
-    power = PowerSampler(dev.index or 0)
-    power.start()
+    power = PowerSampler(dev.index or 0) if args.full else None
+    if power:
+        power.start()
     ops.trace_mark(False)
     t0 = time.perf_counter()
     for _ in range(args.steps):
@@ -524,9 +588,22 @@ def main_c1(args, dev):
     ops.trace_mark(True)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
-    power = power.stop()
+    power = power.stop() if power else None
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, out, ("labels", "u_preds", "name_idx"), nouns)
     u_true = y.cpu().numpy()[~mask_lab]
     name_hits = float(np.mean(np.array([int(nm.split("_")[1]) for nm in out["cand_names"]])[out["u_preds"]] == u_true))
+    line = {"metric": "images/sec end-to-end (encode+sim+k-means) on 224^2 synth, 21k vocab", "value": round(n * args.steps / dt, 2), "unit": "images/sec",
+            "n_gpus": 1, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 3), "higher_is_better": True,
+            "scaling": "weak", "vs_baseline": None, "dtype": "f16", "data": "synthetic",
+            "config": {"workload": CONFIGS["c1"]["workload"] % v if args.cluster == "KM" else (CONFIGS["c1"]["workload"] % v).replace(
+                           "sklearn-style KMeans (--cluster KM, n_init=10)", "SSKM (10 restarts x 10 iters)"),
+                       "cluster": args.cluster, "images_per_gpu": n, "vocab": v, "n_cluster": k, "encode_batch": None,
+                       "weights": "none: cached features (synthetic, seeded)", "parallelism": "dp1"},
+            "vote_iters": out["vote_iters"], "synthetic_name_accuracy": round(name_hits, 4)}
+    if not args.full:
+        print(json.dumps(line), flush=True)
+        return
     # the E-step call on the fit's rows and final centres (HIP events, 50 calls): the HBM-bound kernel of this path
     xu = out["u_feats"].contiguous()
     cent = torch.as_tensor(out["kmeans"].cluster_centers_).to(dev).to(torch.float32).contiguous()
@@ -544,15 +621,8 @@ def main_c1(args, dev):
     dp = (d + 127) // 128 * 128
     by = nu * dp * 2 + 4 * nu + ((k + 127) // 128 * 128) * dp * 2
     sclk = (power or {}).get("sclk_mhz_median")
-    line = {"metric": "images/sec end-to-end (encode+sim+k-means) on 224^2 synth, 21k vocab", "value": round(n * args.steps / dt, 2), "unit": "images/sec",
-            "n_gpus": 1, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 3), "higher_is_better": True,
-            "scaling": "weak", "vs_baseline": None, "dtype": "f16", "data": "synthetic",
-            "config": {"workload": CONFIGS["c1"]["workload"] % v if args.cluster == "KM" else (CONFIGS["c1"]["workload"] % v).replace(
-                           "sklearn-style KMeans (--cluster KM, n_init=10)", "SSKM (10 restarts x 10 iters)"),
-                       "cluster": args.cluster, "images_per_gpu": n, "vocab": v, "n_cluster": k, "encode_batch": None,
-                       "weights": "none: cached features (synthetic, seeded)", "parallelism": "dp1"},
+    line.update({
             "stage_ms_per_step": {kk: round(vv / args.steps, 3) for kk, vv in stage_ms.items()}, "encode_tflops": None,
-            "vote_iters": out["vote_iters"], "synthetic_name_accuracy": round(name_hits, 4),
             "roofline": {"bound": "hbm", "achieved": round(by / t_e / 1e9, 1), "peak": PEAK_HBM_GBS, "unit": "GB/s", "frac": round(by / t_e / (PEAK_HBM_GBS * 1e9), 4),
                          "traffic": None, "kernel": "scd_kmeans_estep call (centre prep + filter + refine), N=%d D=%d K=%d, this run's rows / final centres; "
                                                     "Infinity-Cache resident operand (%.1f MB): a latency-bound launch, not a streaming one" % (nu, d, k, by / 2 ** 20),
@@ -561,9 +631,55 @@ def main_c1(args, dev):
                                  "Lloyd iterations driven from C): no kernel of it approaches a roofline, the stage times are the measurement" % k},
             "board_power": power, "sclk_mhz_median": sclk, "encode_cycles_per_image": None,
             "km_fit": {"n_iter_kept_start": int(getattr(out["kmeans"], "n_iter_", 0)), "fit_ms_per_step": round(stage_ms.get("kmeans", 0.0) / args.steps, 3)},
-            "secondary_rooflines": []}
+            "secondary_rooflines": []})
     line["cpu_baseline"] = None if args.no_cpu_baseline else cpu_baseline_child()
     print(json.dumps(line), flush=True)
+
+
+def full_line(line, args, out, model, wt, nouns, dev, world, stage_ms, power, mask_lab, n_cls):
+    """--full: the stage times, rooflines, board power and cpu_baseline of the run, added to `line`."""
+    roof = dominant_kernel_roofline(*model.visual.enc.timing(False))
+    enc_s = stage_ms.get("encode", 0.0) / 1e3 / args.steps
+    line.update({
+        "stage_ms_per_step": {k: round(v / args.steps, 2) for k, v in stage_ms.items()},
+        "encode_tflops": round(args.images * FLOP_PER_IMAGE / max(enc_s, 1e-9) / 1e12, 1),
+        "roofline": roof,
+        "board_power": power,
+    })
+    # clock-normalised encode cost: boxes of this pool hold 1.69-1.88 GHz at the same 1,400-W cap, so images/s moves by +-3 % box to
+    # box with the same binary; shader cycles per image (median sclk over the timed steps x encode seconds / images) does not
+    sclk = (power or {}).get("sclk_mhz_median")
+    line["sclk_mhz_median"] = sclk
+    line["encode_cycles_per_image"] = round(sclk * 1e6 * enc_s / args.images) if (sclk and enc_s > 0) else None
+    if args.config == "c3":
+        line["encode_cycles_per_image_note"] = "two towers (DINO / GCD + CLIP) per image"
+    if args.config == "c3":
+        km = out["kmeans"]
+        line["consskm"] = {"fit_ms_per_step": line["stage_ms_per_step"].get("kmeans"), "transport_solves_per_fit": km.stats.get("transport_solves"),
+                           "host_threads": len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else os.cpu_count(),
+                           "phase_ms_last_fit": km.stats.get("phase_ms"),       # SCD_CONSSKM_PROFILE=1 only (a device sync per iteration)
+                           "cluster_sizes_min_max": [int(np.bincount(out["labels"][int(mask_lab.sum()):], minlength=n_cls).min()),
+                                                     int(np.bincount(out["labels"][int(mask_lab.sum()):], minlength=n_cls).max())],
+                           "note": "the restarts' flow problems of an iteration are solved on host threads (scd_transport_solve_batch); "
+                                   "the step's images/s counts each image once although two towers encode it"}
+        line["secondary_rooflines"] = []
+    else:
+        line["secondary_rooflines"] = secondary_rooflines(out, out.get("wt", wt), dev, km_fit=(args.cluster == "KM"))
+    if args.config == "c5":
+        # the text tower (row a4): GEMM FLOPs actually executed after the context trimming = 3 x its fc1 launches' FLOPs (per row and
+        # layer QKV 3 w^2 + proj w^2 + fc1 4 w^2 + fc2 4 w^2 multiply-adds, fc1 is a third; attention and the pooling not counted) over
+        # the "text_tower" stage's time (tokenisation on the host runs behind the device work and is inside it)
+        t_ms, t_n, t_fl = model._text.timing(False)
+        tt_s = stage_ms.get("text_tower", 0.0) / 1e3 / args.steps
+        prompts = len(nouns) * 80 // world
+        line["secondary_rooflines"].insert(0, {
+            "kernel": "CLIP text tower inside the step: zeroshot_classifier%s over %d names x 80 prompts per rank (trimmed context, four length groups per 256 names)"
+                      % ("_sharded + all-gather" if world > 1 else "", len(nouns) // world),
+            "bound": "mfma", "achieved": round(3.0 * t_fl / args.steps / max(tt_s, 1e-9) / 1e12, 1), "peak": PEAK_F16_TFLOPS, "unit": "TFLOP/s",
+            "frac": round(3.0 * t_fl / args.steps / max(tt_s, 1e-9) / (PEAK_F16_TFLOPS * 1e12), 4), "stage_ms": round(tt_s * 1e3, 1),
+            "prompts_per_s": round(prompts / max(tt_s, 1e-9)), "gemm_gflop_per_prompt_executed": round(3.0 * t_fl / args.steps / max(prompts, 1) / 1e9, 3),
+            "fc1_launches_per_step": t_n // max(args.steps, 1), "fc1_kernel_frac_of_peak": round(t_fl / max(t_ms, 1e-9) / 1e9 / PEAK_F16_TFLOPS, 4)})
+    line["cpu_baseline"] = None if args.no_cpu_baseline else cpu_baseline_child()
 
 
 def main():
@@ -668,7 +784,7 @@ def main():
     stage_ms = {}
 
     def step(i, timed):
-        timers = [] if timed else None
+        timers = [] if (timed and args.full) else None
         if args.config == "c3":
             out = pipeline.run_ptsup(model, feat_model, images, mask_lab, l_targets, wt, nouns, lab_names, n_cls, topk=2, num_common_vote=5,
                                      num_common_linear=2, size_min=50, size_max=1000, batch=args.batch, seed=i, timers=timers)
@@ -678,6 +794,7 @@ def main():
                                build_vocab=build_vocab, text_feats=text_feats)
         if timed:
             torch.cuda.synchronize()
+        if timers:
             for (n0, e0), (n1, e1) in zip(timers[:-1], timers[1:]):
                 stage_ms[n1] = stage_ms.get(n1, 0.0) + e0.elapsed_time(e1)
         return out
@@ -685,10 +802,12 @@ def main():
     for i in range(args.warmup):
         out = step(i, False)
     barrier()
-    model.visual.enc.timing(True)
-    if args.config == "c5":
-        model._text.timing(True)        # the text tower's fc1 launches, bracketed by HIP events like the image tower's
-    power = PowerSampler(local_rank) if rank == 0 else None       # a host thread reading sysfs: nothing enters the stream
+    power = None
+    if args.full:
+        model.visual.enc.timing(True)
+        if args.config == "c5":
+            model._text.timing(True)        # the text tower's fc1 launches, bracketed by HIP events like the image tower's
+        power = PowerSampler(local_rank) if rank == 0 else None       # a host thread reading sysfs: nothing enters the stream
     if power:
         power.start()
     _ops.trace_mark(False)              # an empty marker kernel in front of the timed steps and one behind them: a kernel trace of this
@@ -704,6 +823,8 @@ def main():
         import torch.distributed as dist
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
     dt = float(tt.item())
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, out, ("feats", "labels", "u_preds", "name_idx") + (("wt",) if build_vocab else ()), nouns)
 
     # quality of the synthetic run (not part of the metric): cluster purity and names found
     yn = y.cpu().numpy()
@@ -714,8 +835,6 @@ def main():
     if rank == 0:
         total_images = args.images * world * args.steps
         value = total_images / dt
-        roof = dominant_kernel_roofline(*model.visual.enc.timing(False))
-        enc_s = stage_ms.get("encode", 0.0) / 1e3 / args.steps
         line = {
             "metric": "images/sec end-to-end (encode+sim+k-means) on 224^2 synth, 21k vocab",
             "value": round(value, 2), "unit": "images/sec", "n_gpus": (dist.get_world_size() if world > 1 else 1), "steps": args.steps, "warmup": args.warmup,
@@ -726,47 +845,12 @@ def main():
                        "cluster": args.cluster,
                        "images_per_gpu": args.images, "vocab": args.vocab, "n_cluster": n_cls, "encode_batch": args.batch,
                        "weights": "random-init (seeded), no checkpoint offline", "parallelism": "dp%d" % world},
-            "stage_ms_per_step": {k: round(v / args.steps, 2) for k, v in stage_ms.items()},
-            "encode_tflops": round(args.images * FLOP_PER_IMAGE / max(enc_s, 1e-9) / 1e12, 1),
             "vote_iters": out["vote_iters"], "synthetic_name_accuracy": round(name_hits, 4),
-            "roofline": roof,
-            "board_power": power,
         }
-        # clock-normalised encode cost: boxes of this pool hold 1.69-1.88 GHz at the same 1,400-W cap, so images/s moves by +-3 % box to
-        # box with the same binary; shader cycles per image (median sclk over the timed steps x encode seconds / images) does not
-        sclk = (power or {}).get("sclk_mhz_median")
-        line["sclk_mhz_median"] = sclk
-        line["encode_cycles_per_image"] = round(sclk * 1e6 * enc_s / args.images) if (sclk and enc_s > 0) else None
         if args.config == "c3":
-            line["encode_cycles_per_image_note"] = "two towers (DINO / GCD + CLIP) per image"
-        if args.config == "c3":
-            km = out["kmeans"]
             line["config"]["cluster"] = "ConSSKM"
-            line["consskm"] = {"fit_ms_per_step": line["stage_ms_per_step"].get("kmeans"), "transport_solves_per_fit": km.stats.get("transport_solves"),
-                               "host_threads": len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else os.cpu_count(),
-                               "phase_ms_last_fit": km.stats.get("phase_ms"),       # SCD_CONSSKM_PROFILE=1 only (a device sync per iteration)
-                               "cluster_sizes_min_max": [int(np.bincount(out["labels"][int(mask_lab.sum()):], minlength=n_cls).min()),
-                                                         int(np.bincount(out["labels"][int(mask_lab.sum()):], minlength=n_cls).max())],
-                               "note": "the restarts' flow problems of an iteration are solved on host threads (scd_transport_solve_batch); "
-                                       "the step's images/s counts each image once although two towers encode it"}
-            line["secondary_rooflines"] = []
-        else:
-            line["secondary_rooflines"] = secondary_rooflines(out, out.get("wt", wt), dev, km_fit=(args.cluster == "KM"))
-        if args.config == "c5":
-            # the text tower (row a4): GEMM FLOPs actually executed after the context trimming = 3 x its fc1 launches' FLOPs (per row and
-            # layer QKV 3 w^2 + proj w^2 + fc1 4 w^2 + fc2 4 w^2 multiply-adds, fc1 is a third; attention and the pooling not counted) over
-            # the "text_tower" stage's time (tokenisation on the host runs behind the device work and is inside it)
-            t_ms, t_n, t_fl = model._text.timing(False)
-            tt_s = stage_ms.get("text_tower", 0.0) / 1e3 / args.steps
-            prompts = len(nouns) * 80 // world
-            line["secondary_rooflines"].insert(0, {
-                "kernel": "CLIP text tower inside the step: zeroshot_classifier%s over %d names x 80 prompts per rank (trimmed context, four length groups per 256 names)"
-                          % ("_sharded + all-gather" if world > 1 else "", len(nouns) // world),
-                "bound": "mfma", "achieved": round(3.0 * t_fl / args.steps / max(tt_s, 1e-9) / 1e12, 1), "peak": PEAK_F16_TFLOPS, "unit": "TFLOP/s",
-                "frac": round(3.0 * t_fl / args.steps / max(tt_s, 1e-9) / (PEAK_F16_TFLOPS * 1e12), 4), "stage_ms": round(tt_s * 1e3, 1),
-                "prompts_per_s": round(prompts / max(tt_s, 1e-9)), "gemm_gflop_per_prompt_executed": round(3.0 * t_fl / args.steps / max(prompts, 1) / 1e9, 3),
-                "fc1_launches_per_step": t_n // max(args.steps, 1), "fc1_kernel_frac_of_peak": round(t_fl / max(t_ms, 1e-9) / 1e9 / PEAK_F16_TFLOPS, 4)})
-        line["cpu_baseline"] = None if args.no_cpu_baseline else cpu_baseline_child()
+        if args.full:
+            full_line(line, args, out, model, wt, nouns, dev, world, stage_ms, power, mask_lab, n_cls)
         print(json.dumps(line), flush=True)
     if world > 1:
         import torch.distributed as dist

@@ -1,5 +1,5 @@
 import sys, os, torch
-sys.path.insert(0, "/root/repo" if os.path.exists("/root/repo/scd_amd") else os.environ.get("GRAFT_REPO_ROOT", "."))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from scd_amd.clip import weights as W
 from scd_amd.clip.model import CLIP
 sd = W.synthetic_clip_state_dict(seed=3, cfg=dict(v_layers=2, t_layers=2))

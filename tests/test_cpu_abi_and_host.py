@@ -545,3 +545,38 @@ def test_bench_power_sampler_reads_hwmon(tmp_path, monkeypatch):
     ps = bench.PowerSampler(0)
     ps.start()
     assert ps.stop() is None
+
+
+def test_bench_dump_outputs_sample_and_types(tmp_path):
+    """bench.dump_outputs (--dump-outputs DIR): one .npy per output in float32 / float64, integers exact, a matrix above DUMP_MAX_ELEMS
+    cut to the same seeded rows on every call (row numbers beside it), the candidate names as vocabulary rows, the 64-MB limit held."""
+    import importlib.util
+    import types
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    g = torch.Generator().manual_seed(0)
+    nouns = ["name_%05d" % i for i in range(5000)]
+    out = dict(feats=torch.randn(40000, 64, generator=g).half(), labels=torch.randint(0, 50, (40000,), generator=g),
+               u_preds=np.arange(30000) % 50, name_idx=torch.randint(0, 5000, (40000, 3), generator=g),
+               cand_names=nouns[:49] + ["not_in_vocab"], vote_iters=3, kmeans=types.SimpleNamespace(cluster_centers_=torch.randn(50, 64, generator=g)))
+    dirs = [tmp_path / "a", tmp_path / "b"]
+    for d in dirs:
+        bench.dump_outputs(str(d), out, ("feats", "labels", "u_preds", "name_idx"), nouns)
+    names = sorted(p.name for p in dirs[0].iterdir())
+    assert names == sorted(["feats.npy", "feats_rows.npy", "labels.npy", "u_preds.npy", "name_idx.npy", "cand_name_idx.npy",
+                            "cluster_centers.npy", "vote_iters.npy"])
+    total = 0
+    for nm in names:
+        a, b = np.load(dirs[0] / nm), np.load(dirs[1] / nm)
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b)
+        total += (dirs[0] / nm).stat().st_size
+    assert total <= bench.DUMP_MAX_BYTES
+    rows = np.load(dirs[0] / "feats_rows.npy").astype(np.int64)
+    feats = np.load(dirs[0] / "feats.npy")
+    assert feats.size <= bench.DUMP_MAX_ELEMS and len(rows) == feats.shape[0] and np.all(np.diff(rows) > 0)
+    assert np.array_equal(feats, out["feats"][torch.as_tensor(rows)].float().numpy())
+    assert np.array_equal(np.load(dirs[0] / "name_idx.npy"), out["name_idx"].numpy().astype(np.float64))
+    cand = np.load(dirs[0] / "cand_name_idx.npy")
+    assert np.array_equal(cand[:49], np.arange(49)) and cand[49] == -1
+    assert np.load(dirs[0] / "vote_iters.npy").tolist() == [3.0]

@@ -2079,7 +2079,7 @@ def test_bench_config_c3_small(ops):
     env = dict(os.environ)
     env.pop("SCD_HIP_LIB", None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--config", "c3", "--steps", "1", "--warmup", "1", "--images", "3000", "--n-cluster", "24",
-           "--vocab", "2048", "--batch", "665", "--no-cpu-baseline"]
+           "--vocab", "2048", "--batch", "665", "--full", "--no-cpu-baseline"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
     d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
@@ -2097,7 +2097,7 @@ def test_bench_config_c1(ops):
     import sys
     env = dict(os.environ)
     env.pop("SCD_HIP_LIB", None)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--config", "c1", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--config", "c1", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
     d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
@@ -2120,7 +2120,7 @@ def test_bench_config_c5_small(ops, gpus):
     env = dict(os.environ, SCD_DIST_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     env.pop("SCD_HIP_LIB", None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--config", "c5", "--gpus", str(gpus), "--steps", "1", "--warmup", "1", "--images", "1500",
-           "--n-cluster", "12", "--vocab", "1536", "--batch", "665", "--no-cpu-baseline"]
+           "--n-cluster", "12", "--vocab", "1536", "--batch", "665", "--full", "--no-cpu-baseline"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -2131,6 +2131,37 @@ def test_bench_config_c5_small(ops, gpus):
     assert "text tower" in tt["kernel"] and tt["bound"] == "mfma" and 0 < tt["frac"] < 1 and tt["fc1_launches_per_step"] > 0
     assert 0.05 < tt["gemm_gflop_per_prompt_executed"] < 5.96          # trimmed: below the full-length 5.96 GFLOP per prompt
     assert d["vote_iters"] >= 1 and d["synthetic_name_accuracy"] > 0.6
+
+
+def test_bench_plain_run_and_dump_outputs(ops, tmp_path):
+    """A plain `python bench.py` (no --full) at a tiny size, twice with --dump-outputs: the line carries the headline fields and
+    none of what --full adds, --steps is the number of timed steps, and the two runs' outputs are the same bits."""
+    import json
+    import subprocess
+    import sys
+    env = dict(os.environ)
+    env.pop("SCD_HIP_LIB", None)
+    lines = []
+    for tag in ("a", "b"):
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--images", "1200", "--n-cluster", "12",
+               "--vocab", "1024", "--batch", "665", "--dump-outputs", str(tmp_path / tag)]
+        r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
+        out = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(out) == 1
+        lines.append(json.loads(out[0]))
+    d = lines[0]
+    assert d["steps"] == 2 and d["warmup"] == 1 and d["unit"] == "images/sec" and d["higher_is_better"] is True and d["dtype"] == "f16"
+    assert d["value"] > 0 and abs(d["value"] - 1200 / (d["ms_per_step"] / 1e3)) <= 1e-2 * d["value"]
+    assert not {"roofline", "secondary_rooflines", "cpu_baseline", "stage_ms_per_step", "board_power"} & set(d)
+    names = sorted(p.name for p in (tmp_path / "a").iterdir())
+    assert {"feats.npy", "labels.npy", "u_preds.npy", "name_idx.npy", "cand_name_idx.npy", "cluster_centers.npy"} <= set(names)
+    assert names == sorted(p.name for p in (tmp_path / "b").iterdir())
+    for nm in names:
+        a, b = np.load(tmp_path / "a" / nm), np.load(tmp_path / "b" / nm)
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b, equal_nan=True), nm
+    assert np.load(tmp_path / "a" / "feats.npy").shape == (1200, 512)
+    assert np.load(tmp_path / "a" / "labels.npy").shape == (1200,)
 
 
 def test_two_ranks_one_gpu_sharded_kmeans(ops):

@@ -2,7 +2,7 @@
 # Evidence steps on the GPU box, one script for every round (round 6 folded the per-round tools/gpu_r0N_*.sh one-offs into it; those are
 # kept under tools/history/ because committed profiles cite them):   tools/evidence.sh STEP [ARGS]     outputs under gpurun_out/$ROUND
 #   pytest TAG [pytest args]     GPU suite (or a -k subset) -> pytest_TAG.txt
-#   bench TAG [bench.py args]    one bench line -> bench_TAG.json, summary printed
+#   bench TAG [bench.py args]    one `bench.py --full` line -> bench_TAG.json, summary printed
 #   bench_prof TAG [bench args]  rocprofv3 kernel stats of the TIMED region of the bench command (marker kernels) -> ${ROUND}_bench_TAG_kernel_stats.csv
 #   prof TAG script.py [args]    rocprofv3 kernel stats of any python tool -> prof_TAG/kernel_stats.csv
 #   ab LIB...                    same-box whole-bench comparison of the default library and builds scd_amd/lib/libscd_hip_LIB.so (two repetitions)
@@ -42,7 +42,7 @@ PY
 c3_ab)     # bench.py --config c3 on the default library and the given builds, then once more with the ConSSKM phase profile
   for lib in default "$@"; do
     if [ $lib = default ]; then unset SCD_HIP_LIB; else export SCD_HIP_LIB=$R/scd_amd/lib/libscd_hip_$lib.so; fi
-    timeout -k 10 400 python bench.py --config c3 --steps 3 --warmup 1 --no-cpu-baseline > $out/c3_$lib.json 2> $out/c3.err || { tail -n 20 $out/c3.err; exit 1; }
+    timeout -k 10 400 python bench.py --config c3 --steps 3 --warmup 1 --full --no-cpu-baseline > $out/c3_$lib.json 2> $out/c3.err || { tail -n 20 $out/c3.err; exit 1; }
     python - <<PY
 import json
 d=json.load(open("$out/c3_$lib.json"))
@@ -50,7 +50,7 @@ print("lib %-10s %9.1f images/s  stages %s  fit %s ms" % ("$lib", d["value"], d[
 PY
   done
   unset SCD_HIP_LIB
-  SCD_CONSSKM_PROFILE=1 timeout -k 10 400 python bench.py --config c3 --steps 2 --warmup 1 --no-cpu-baseline > $out/c3_phases.json 2> $out/c3.err || { tail -n 20 $out/c3.err; exit 1; }
+  SCD_CONSSKM_PROFILE=1 timeout -k 10 400 python bench.py --config c3 --steps 2 --warmup 1 --full --no-cpu-baseline > $out/c3_phases.json 2> $out/c3.err || { tail -n 20 $out/c3.err; exit 1; }
   python -c "import json; d=json.load(open('$out/c3_phases.json')); print('phases of the last fit', d['consskm']['phase_ms_last_fit'], 'fit', d['consskm']['fit_ms_per_step'])" ;;
 c3_tests)
   timeout -k 10 900 python -m pytest tests -x -q -m gpu -k "transport or consskm or constrained or c3 or ptsup or dist" > $out/c3_tests.txt 2>&1; rc=$?
@@ -68,7 +68,7 @@ pytest)    # tools/evidence.sh pytest TAG -k EXPR
   echo "[pytest $tag] rc=$rc"; tail -n 3 $out/pytest_$tag.txt; [ $rc -eq 0 ] || { tail -n 60 $out/pytest_$tag.txt; exit 1; } ;;
 bench)     # tools/evidence.sh bench TAG ARGS...  -> $out/bench_TAG.json
   tag=$1; shift
-  timeout -k 10 900 python bench.py "$@" > $out/bench_$tag.json 2> $out/bench_$tag.err || { tail -n 30 $out/bench_$tag.err; exit 1; }
+  timeout -k 10 900 python bench.py --full "$@" > $out/bench_$tag.json 2> $out/bench_$tag.err || { tail -n 30 $out/bench_$tag.err; exit 1; }
   python - <<PY
 import json
 d=json.load(open("$out/bench_$tag.json"))
@@ -94,7 +94,7 @@ ab)
   for rep in 1 2; do
   for lib in default "$@"; do
     if [ $lib = default ]; then unset SCD_HIP_LIB; else export SCD_HIP_LIB=$R/scd_amd/lib/libscd_hip_$lib.so; fi
-    timeout -k 10 400 python bench.py --steps 2 --warmup 1 --no-cpu-baseline > $out/ab.json 2> $out/ab.err || { tail -n 20 $out/ab.err; exit 1; }
+    timeout -k 10 400 python bench.py --steps 2 --warmup 1 --full --no-cpu-baseline > $out/ab.json 2> $out/ab.err || { tail -n 20 $out/ab.err; exit 1; }
     python - <<PY | tee -a $out/ab.txt
 import json
 d=json.load(open("$out/ab.json"))
