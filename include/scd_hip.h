@@ -412,6 +412,36 @@ int scd_clip_encode_text_len(scd_handle h, const scd_encoder* e, const int32_t* 
 int scd_gemm_f16(scd_handle h, const void* A, const void* W, const float* bias, const void* residual, void* C,
                  int64_t m, int n, int k, int act, void* stream);
 
+/* ---- image preprocessing: CLIP's `preprocess` (main_unsup.py:237,271, applied by the DataLoader at :271-289) on decoded images -
+ *      torchvision Resize(size, BICUBIC) on a PIL RGB image (Pillow Resample.c, uint8, separable, int32 taps with 22 fraction bits),
+ *      CenterCrop(crop), ToTensor + Normalize through a lookup table - bit for bit (docs/design/ingest.md).
+ * Plans (per image size, cached by the library; host only):
+ *   scd_image_geometry: out6 = {resized w, resized h, crop left, crop top, first source row read, source rows read};
+ *   scd_image_plan_axis: Pillow's taps of outputs off .. off + n - 1 of an in_size -> out_size bicubic resize: first[n] input index,
+ *     ntaps[n], taps = the int32 weights of every output in order; taps == NULL only reports the total (n_taps_out);
+ *   scd_image_batch_plan: descs[batch] and the packed plan (int32 [plan_len]) of a batch of images of sizes wh = {w0, h0, w1, h1, ...}
+ *     whose packed uint8 RGB HWC pixels lie back to back (pixel_bytes in all); ws_bytes: workspace of scd_image_preprocess.  With
+ *     plan == NULL (descs may be NULL too) only the three sizes are reported.
+ * scd_image_preprocess: descs / plan (device copies of scd_image_batch_plan's), lut fp16 [3][256] = ((v / 255 - mean) / std).half()
+ *   per channel, out fp16 [batch, 3, crop, crop] (NCHW), crop <= 256.  Descriptors and taps are checked against pixel_bytes, plan_len
+ *   and ws_bytes on the device by both passes: nothing is read outside them, and an image whose descriptor would (or a column whose
+ *   taps would) gets NaN pixels there.  size and crop of the planners: 1 <= crop <= size <= 65536; image edges 1 .. 65536. */
+typedef struct scd_image_desc {
+    int64_t src_off;   /* byte offset of the image's pixels in `pixels` */
+    int64_t tmp_off;   /* byte offset of its horizontal-pass band in the workspace */
+    int32_t w, h;      /* source size */
+    int32_t plan_x;    /* int32 offset of the horizontal plan block in `plan` */
+    int32_t plan_y;    /* ... of the vertical one */
+    int32_t row0, rows;/* source rows the horizontal pass covers */
+} scd_image_desc;
+int scd_image_geometry(int w, int h, int size, int crop, int32_t* out6);
+int scd_image_plan_axis(int in_size, int out_size, int off, int n, int32_t* first, int32_t* ntaps, int32_t* taps, int64_t taps_cap,
+                        int64_t* n_taps_out);
+int scd_image_batch_plan(const int32_t* wh, int batch, int size, int crop, scd_image_desc* descs, int32_t* plan, int64_t plan_cap,
+                         int64_t* plan_len, int64_t* pixel_bytes, int64_t* ws_bytes);
+int scd_image_preprocess(scd_handle h, const uint8_t* pixels, int64_t pixel_bytes, const scd_image_desc* descs, const int32_t* plan,
+                         int64_t plan_len, int batch, int crop, const void* lut, void* out, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

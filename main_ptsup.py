@@ -3,7 +3,7 @@
 the same flags (:227-244) and stage order, on libscd_hip.so.  Differences from main_unsup.py follow the reference:
 the cluster cache name has no n_cluster (:385), TOP_K = 5 with raw logits (no softmax, :526-545), the zero-shot sACC lower /
 upper bounds (:548-585), votes only over clusters without labelled samples, names of the labelled classes excluded and then
-re-added (:588-676).  See main_unsup.py for the data conventions (--class_names, --images_pt, cache files)."""
+re-added (:588-676).  See main_unsup.py for the data conventions (--class_names, --images_pt / --image_list, cache files)."""
 import json
 import os
 import sys
@@ -56,8 +56,7 @@ def main(argv=None):
             raise SystemExit("main_ptsup.py needs --class_names (JSON {original class name: class index}): the vote keeps the names "
                              "of the labelled classes fixed (main_ptsup.py:597-603)")
         feat_model = mu.load_feat_model(args, model) if args.extract_feat else None
-        data = mu.load_or_extract(args, feat_model, args.feat_model, f'{args.feat_model}_{args.dataset_name}_all.pt')
-        cdata = mu.load_or_extract(args, model, 'clip', f'clip_{args.dataset_name}_all.pt')
+        data, cdata = mu.extract_or_load_all(args, feat_model, model)
         all_feats, mask_lab, mask_cls, targets = data['all_feats'], data['mask_lab'], data['mask_cls'], data['targets']
         clip_all = torch.as_tensor(cdata['all_feats']).to(dev).half()
         nouns, zw, wt = mu.load_vocabulary(args, dev)

@@ -10,7 +10,11 @@ Here every stage starts from the reference's own cache files under --root_dir, b
   zeroshot_weights/zeroshot_weights_all_{nouns|wikibird|wikidog}_vit_b_16.pt   tensor [512, V]        (:389-394)
 The two things the reference takes from its dataset objects are passed as files instead:
   --class_names  JSON {original class name: class index}  (`datasets['test'].class_to_idx` / the sorted breed / wnid tables)
-  --images_pt    torch file dict(images [N,3,224,224] preprocessed, targets [N], mask_lab [N]) for --extract_feat true
+  --images_pt    torch file dict(images [N,3,224,224] preprocessed, targets [N], mask_lab [N]) for --extract_feat true, or
+  --image_list   CSV of `path,target,labelled` rows (paths relative to the CSV's directory; labelled rows first, MergedDataset order,
+                 data_utils.py:12-37) for --extract_feat true straight from image files: one PIL decode per image, CLIP's
+                 `preprocess` (:271) on the device bit for bit, both towers fed from it, and the two caches above written
+                 (scd_amd/images.py; scd_amd.images.list_image_folder lists an ImageFolder tree and its class_to_idx)
 With --synthetic everything is generated from seeds (no dataset / checkpoint needed).
 """
 import argparse
@@ -62,6 +66,7 @@ def build_parser():
     p.add_argument('--synthetic_vocab', type=int, default=21000)
     p.add_argument('--class_names', type=str, default='', help='JSON {original class name: class index} of the data set')
     p.add_argument('--images_pt', type=str, default='', help='preprocessed images for --extract_feat true')
+    p.add_argument('--image_list', type=str, default='', help='CSV path,target,labelled of image files for --extract_feat true')
     return p
 
 
@@ -92,7 +97,7 @@ def load_or_extract(args, model, feat_model_name, out_name):
     if not args.extract_feat:
         return torch.load(path, weights_only=False)
     if not args.images_pt:
-        raise SystemExit("--extract_feat true needs --images_pt (the reference's dataset classes are out of scope)")
+        raise SystemExit("--extract_feat true needs --images_pt or --image_list (the reference's dataset classes are out of scope)")
     blob = torch.load(args.images_pt, weights_only=False)
     images, targets, mask_lab = blob['images'], np.asarray(blob['targets']), np.asarray(blob['mask_lab'])
     args_feat = argparse.Namespace(feat_model=feat_model_name,
@@ -105,6 +110,25 @@ def load_or_extract(args, model, feat_model_name, out_name):
     os.makedirs(fdir, exist_ok=True)
     torch.save(data, path)
     return data
+
+
+def extract_or_load_all(args, feat_model, clip_model):
+    """The two feature dicts of :294-313 ({feat_model} and clip).  With --extract_feat true and --image_list: both from ONE pass over
+    the image files (scd_amd.images), written to the same cache files as load_or_extract writes; otherwise load_or_extract twice."""
+    fname, cname = f'{args.feat_model}_{args.dataset_name}_all.pt', f'clip_{args.dataset_name}_all.pt'
+    if not (args.extract_feat and args.image_list):
+        return load_or_extract(args, feat_model, args.feat_model, fname), load_or_extract(args, clip_model, 'clip', cname)
+    if args.images_pt:
+        raise SystemExit("--images_pt and --image_list are alternatives: pass one")
+    from scd_amd import images as img
+    paths, targets, mask_lab = img.read_image_list(args.image_list)
+    models = {args.feat_model: feat_model, 'clip': clip_model}
+    out = img.extract_features_from_files(paths, targets, mask_lab, models)
+    fdir = os.path.join(args.root_dir, 'extracted_features')
+    os.makedirs(fdir, exist_ok=True)
+    torch.save(out[args.feat_model], os.path.join(fdir, fname))
+    torch.save(out['clip'], os.path.join(fdir, cname))
+    return out[args.feat_model], out['clip']
 
 
 def load_feat_model(args, clip_model):
@@ -163,8 +187,7 @@ def main(argv=None):
         cidx_to_cname = {c: nouns[c] for c in range(k)}
     else:
         feat_model = load_feat_model(args, model) if args.extract_feat else None
-        data = load_or_extract(args, feat_model, args.feat_model, f'{args.feat_model}_{args.dataset_name}_all.pt')
-        cdata = load_or_extract(args, model, 'clip', f'clip_{args.dataset_name}_all.pt')
+        data, cdata = extract_or_load_all(args, feat_model, model)
         all_feats, mask_lab, mask_cls, targets = data['all_feats'], data['mask_lab'], data['mask_cls'], data['targets']
         clip_all = torch.as_tensor(cdata['all_feats']).to(dev).half()
         nouns, zw, wt = load_vocabulary(args, dev)

@@ -137,7 +137,17 @@ SIGNATURES = {
     "scd_clip_encode_text": (_i, [_vp, _vp, _vp, _i, _vp, _i, _vp, _sz, _vp]),
     "scd_clip_encode_text_len": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _vp, _sz, _vp]),
     "scd_gemm_f16": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _i, _vp]),
+    "scd_image_geometry": (_i, [_i, _i, _i, _i, _vp]),
+    "scd_image_plan_axis": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _i64, _vp]),
+    # wh, batch, size, crop, descs, plan, plan_cap, plan_len, pixel_bytes, ws_bytes
+    "scd_image_batch_plan": (_i, [_vp, _i, _i, _i, _vp, _vp, _i64, _vp, _vp, _vp]),
+    # h, pixels, pixel_bytes, descs, plan, plan_len, batch, crop, lut, out, ws, ws_bytes, stream
+    "scd_image_preprocess": (_i, [_vp, _vp, _i64, _vp, _vp, _i64, _i, _i, _vp, _vp, _vp, _sz, _vp]),
 }
+
+# scd_image_desc (include/scd_hip.h) as a numpy record: 40 bytes
+IMAGE_DESC_FIELDS = [("src_off", "<i8"), ("tmp_off", "<i8"), ("w", "<i4"), ("h", "<i4"), ("plan_x", "<i4"), ("plan_y", "<i4"),
+                     ("row0", "<i4"), ("rows", "<i4")]
 
 _lock = threading.Lock()
 _lib = None

@@ -15,13 +15,16 @@ LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libscd_hip.so")
 OBJDIR = os.path.join(LIBDIR, "obj")
 
-SOURCES = ["api.cpp", "munkres.cpp", "munkres_sparse.cpp", "transport.cpp", "comm.cpp", "kmeans.hip", "mstep.hip", "sim.hip", "vote.hip", "gemm.hip", "encoder.hip"]
+SOURCES = ["api.cpp", "munkres.cpp", "munkres_sparse.cpp", "transport.cpp", "comm.cpp", "kmeans.hip", "mstep.hip", "sim.hip", "vote.hip", "gemm.hip", "encoder.hip",
+           "image.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-atomics", "-Wno-unused-result",
          "-fno-gpu-rdc"]
 # per-file additions.  sim.hip: no SLP vectorisation - hipcc pairs scalar float ops of the hand-placed epilogue slots into
 # v_pk_*_f32 (an anti-lever beside MFMAs, MI355X guide) and spills the packed operands it builds for them inside the ring loop
-EXTRA = {"sim.hip": ["-fno-slp-vectorize"]}
+# image.hip: its host planner restates Pillow's double-precision coefficient code, so no contraction of multiply-adds into FMAs and
+# no fast-math there
+EXTRA = {"sim.hip": ["-fno-slp-vectorize"], "image.hip": ["-ffp-contract=off", "-fno-fast-math"]}
 
 
 def _digest(paths):
