@@ -408,6 +408,16 @@ int scd_clip_encode_text(scd_handle h, const scd_encoder* e, const int32_t* toke
  * causal and only the EOT position is read, reference clip model.py encode_text), at ctx_len/77 of the work. */
 int scd_clip_encode_text_len(scd_handle h, const scd_encoder* e, const int32_t* tokens, int batch, int ctx_len, void* out,
                              int normalize, void* ws, size_t ws_bytes, void* stream);
+/* building block exposed for tests: the encoder blocks' attention, softmax(Q K^T / 8) V per (sequence, head), head_dim 64, width =
+ * heads * 64 <= 1024.  qkv fp16 [batch*T][3*width] (Q | K | V, as the QKV GEMM writes them) -> out fp16 [batch*T][width]; causal: query
+ * t sees keys 0..t.  Served: T <= 96, T = 197, and non-causal 192 < T <= 224 (SCD_EINVAL otherwise); the kernel is the one the towers
+ * run at that T. */
+int scd_attention_f16(scd_handle h, const void* qkv, int batch, int T, int width, int heads, int causal, void* out, void* stream);
+/* building block exposed for tests: the last block's one-query attention (the CLS / EOT row).  kv fp16 [batch*T][2*width] (K | V),
+ * q and out fp16 [batch][width], T <= 256; qrow int32 [batch] on the device = b*T + the query's position (causal: the last key it
+ * sees; may be NULL when causal == 0, then every key is seen). */
+int scd_attention_single_query_f16(scd_handle h, const void* kv, const void* q, const int* qrow, int batch, int T, int width,
+                                   int heads, int causal, void* out, void* stream);
 /* building block exposed for tests: C[m,n] = A[m,k] @ W[n,k]^T (+bias)(act)(+residual), fp16 in/out, fp32 accumulate */
 int scd_gemm_f16(scd_handle h, const void* A, const void* W, const float* bias, const void* residual, void* C,
                  int64_t m, int n, int k, int act, void* stream);

@@ -45,6 +45,33 @@ def _attention(x, qkv_w, qkv_b, out_w, out_b, heads, causal):
     return o @ out_w.float().t() + out_b.float()
 
 
+def attention_f64(qkv, batch, T, heads, causal):
+    """float64 restatement of the encoder blocks' attention core on the fp16 values a kernel reads (scd_attention_f16):
+    qkv [batch*T, 3*width] (Q | K | V, heads in 64-wide slices) -> per (sequence, head) P = softmax(Q K^T / 8) with query t
+    seeing keys 0..t when causal, O = P V.  Returns O [batch*T, width] and P [batch, heads, T, T], both float64, on qkv's device."""
+    width = qkv.shape[1] // 3
+    q, k, v = qkv.double().view(batch, T, 3, heads, width // heads).permute(2, 0, 3, 1, 4)
+    s = (q @ k.transpose(-2, -1)) * (width // heads) ** -0.5
+    if causal:
+        s = s.masked_fill(torch.ones(T, T, dtype=torch.bool, device=s.device).triu_(1), float("-inf"))
+    p = s.softmax(dim=-1)
+    return (p @ v).transpose(1, 2).reshape(batch * T, width), p
+
+
+def attention_single_query_f64(kv, q, pos, T, heads, causal):
+    """float64 restatement of the last block's one-query attention (scd_attention_single_query_f16): kv [batch*T, 2*width]
+    (K | V), q [batch, width], pos[b] = the query's position (causal: it sees keys 0..pos[b]).  Returns O [batch, width] and
+    P [batch, heads, T], float64."""
+    batch, width = q.shape
+    k, v = kv.double().view(batch, T, 2, heads, width // heads).permute(2, 0, 3, 1, 4)
+    s = (k @ q.double().view(batch, heads, width // heads, 1)).squeeze(-1) * (width // heads) ** -0.5
+    if causal:
+        keys = torch.arange(T, device=s.device)
+        s = s.masked_fill(keys.view(1, 1, T) > torch.as_tensor(pos, device=s.device).view(batch, 1, 1), float("-inf"))
+    p = s.softmax(dim=-1)
+    return (p.unsqueeze(2) @ v).reshape(batch, width), p
+
+
 def _block(x, g, heads, act, eps, causal):
     """g(name) -> tensor for the canonical per-block names."""
     x = x + _attention(_ln(x, g("ln1_w"), g("ln1_b"), eps), g("qkv_w"), g("qkv_b"), g("proj_w"), g("proj_b"),

@@ -137,6 +137,8 @@ SIGNATURES = {
     "scd_clip_encode_text": (_i, [_vp, _vp, _vp, _i, _vp, _i, _vp, _sz, _vp]),
     "scd_clip_encode_text_len": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _vp, _sz, _vp]),
     "scd_gemm_f16": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _i, _vp]),
+    "scd_attention_f16": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
+    "scd_attention_single_query_f16": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "scd_image_geometry": (_i, [_i, _i, _i, _i, _vp]),
     "scd_image_plan_axis": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _i64, _vp]),
     # wh, batch, size, crop, descs, plan, plan_cap, plan_len, pixel_bytes, ws_bytes

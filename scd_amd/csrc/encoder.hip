@@ -366,6 +366,16 @@ __global__ void __launch_bounds__(256) emit_kernel(const half_t* __restrict__ in
 // read ds_read_b64_tr_b16 (4 keys x 16 d per 16-lane group), so V is staged with plain 16-byte row copies.
 typedef __fp16 fp16x4_t __attribute__((__vector_size__(4 * sizeof(__fp16))));
 
+// Every softmax below takes p = 2^(fma(s, cs, -fl(mx * cs))): the key with the maximum score gets 2^off with off = mx * cs - fl(mx * cs),
+// at most half an ulp of mx * cs - negligible for the scores of real models (|off| < 2^-16 while |mx| < 2^10), but from |mx| ~ 2^27 on
+// off leaves [-0.5, 0.5], from ~2^30 2^off leaves the fp16 range of P, from ~2^34 the fp32 range (64 fp16 products of up to 65504^2
+// reach 2^38): the row became inf / NaN.  When any lane of the wave is there, the exponent arguments are rebuilt as
+// fma(s, cs, -fl(mx * cs)) - off (the maximum key's argument is then exactly 0) and the exp2 step runs with cs = 1, mxs = 0.  A
+// wave-uniform branch that real data never takes: every other input keeps its bits (tests/test_gpu_attention.py largest scores).
+__device__ __forceinline__ bool max_offset_is_large(float mx, float cs, float mxs) {
+    return __builtin_amdgcn_ballot_w64(fabsf(fmaf(mx, cs, -mxs)) > 0.5f) != 0;
+}
+
 template <int NB>   // NB = ceil(T/32): 7 for T=197, 3 for T=77
 __global__ void __launch_bounds__(256, 2) attention_kernel(const half_t* __restrict__ qkv, half_t* __restrict__ out, int T, int width,
                                                            int heads, int causal, int xmode) {
@@ -443,8 +453,17 @@ __global__ void __launch_bounds__(256, 2) attention_kernel(const half_t* __restr
                 mx = fmaxf(mx, v);
             }
         mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-        const float cs = 0.125f * 1.4426950408889634f;
-        const float mxs = mx * cs;
+        float cs = 0.125f * 1.4426950408889634f;
+        float mxs = mx * cs;
+        if (max_offset_is_large(mx, cs, mxs)) {
+            const float off = fmaf(mx, cs, -mxs);
+#pragma unroll
+            for (int kb = 0; kb < NB; ++kb)
+#pragma unroll
+                for (int i = 0; i < 16; ++i) sacc[kb][i] = fmaf(sacc[kb][i], cs, -mxs) - off;
+            cs = 1.f;
+            mxs = 0.f;
+        }
         float sum = 0.f;
 #pragma unroll
         for (int kb = 0; kb < NB; ++kb)
@@ -566,8 +585,15 @@ __global__ void __launch_bounds__(256) attention_short_kernel(const half_t* __re
         mx = fmaxf(mx, v);
     }
     mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-    const float cs = 0.125f * 1.4426950408889634f;
-    const float mxs = mx * cs;
+    float cs = 0.125f * 1.4426950408889634f;
+    float mxs = mx * cs;
+    if (max_offset_is_large(mx, cs, mxs)) {
+        const float off = fmaf(mx, cs, -mxs);
+#pragma unroll
+        for (int i = 0; i < 16; ++i) sacc[i] = fmaf(sacc[i], cs, -mxs) - off;
+        cs = 1.f;
+        mxs = 0.f;
+    }
     float sum = 0.f;
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
@@ -730,7 +756,16 @@ attention_persist_kernel(const half_t* __restrict__ qkv, half_t* __restrict__ ou
         typedef float f2v __attribute__((ext_vector_type(2)));
         typedef _Float16 h2v __attribute__((ext_vector_type(2)));
         const float cs = 0.125f * 1.4426950408889634f;
-        const f2v cs2 = {cs, cs}, nmx2 = {-mx * cs, -mx * cs};
+        f2v cs2 = {cs, cs}, nmx2 = {-mx * cs, -mx * cs};
+        if (max_offset_is_large(mx, cs, mx * cs)) {
+            const float off = fmaf(mx, cs, -(mx * cs));
+#pragma unroll
+            for (int kb = 0; kb < NB; ++kb)
+#pragma unroll
+                for (int e = 0; e < (T197 && kb == NB - 1 ? 4 : 16); ++e) sacc[kb][e] = fmaf(sacc[kb][e], cs, -(mx * cs)) - off;
+            cs2 = f2v{1.f, 1.f};
+            nmx2 = f2v{0.f, 0.f};
+        }
         f2v sum2 = {0.f, 0.f};
         h2v ph[NB][8];
 #pragma unroll
@@ -881,11 +916,19 @@ __global__ void __launch_bounds__(256) attention_single_query_kernel(const half_
         mx = fmaxf(mx, sc[j]);
     }
     mx = wave_max_f32(mx);
-    const float cs = 0.125f * 1.4426950408889634f;
+    float cs = 0.125f * 1.4426950408889634f;
+    float mxs = mx * cs;
+    if (max_offset_is_large(mx, cs, mxs)) {
+        const float off = fmaf(mx, cs, -mxs);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) sc[j] = fmaf(sc[j], cs, -mxs) - off;
+        cs = 1.f;
+        mxs = 0.f;
+    }
     float sum = 0.f;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-        const float pv = __builtin_amdgcn_exp2f(fmaf(sc[j], cs, -mx * cs));     // exp2(-inf) = 0 for masked keys
+        const float pv = __builtin_amdgcn_exp2f(fmaf(sc[j], cs, -mxs));     // exp2(-inf) = 0 for masked keys
         sum += pv;
         ps[wv][lane + 64 * j] = (float)(half_t)pv;
     }
@@ -1072,6 +1115,37 @@ static int attn_xmode() {
     return x;
 }
 
+// The attention of every block (run_blocks) and of scd_attention_f16: qkv [batch*T][3*width] (Q | K | V, heads in 64-wide slices, as the
+// QKV GEMM writes them) -> out [batch*T][width].  The kernel is chosen by T: attention_short_kernel (T <= 32), attention_kernel<2> / <3>
+// (T <= 64 / 96), attention_persist_kernel (non-causal 192 < T <= 224; <true> at T = 197), attention_kernel<7> (T = 197 otherwise).
+// attention_kernel<NB> stages 32*NB keys and computes 32*NB queries, so every other (T, causal) is refused rather than launched.
+static int launch_attention(const half_t* qkv, half_t* out, int batch, int T, int width, int heads, int causal, hipStream_t st) {
+    SCD_REQUIRE(batch > 0 && T > 0 && heads > 0 && width == heads * 64 && width <= 1024,
+                "attention: batch %d, T %d, width %d / heads %d (head_dim must be 64, width <= 1024)", batch, T, width, heads);
+    const int items = batch * heads;
+    static const int attn_persist = getenv("SCD_ATTN_PERSIST") ? atoi(getenv("SCD_ATTN_PERSIST")) : 1;
+    if (T > 192 && T <= 224 && !causal && attn_persist) {
+        constexpr int attn_lds = 2 * 2 * 224 * 128 + 7 * 4096;      // K/V double buffer + the consumers' output patches
+        { const int rc_ = scd_set_max_lds((const void*)attention_persist_kernel<false>, attn_lds); if (rc_) return rc_; }
+        { const int rc_ = scd_set_max_lds((const void*)attention_persist_kernel<true>, attn_lds); if (rc_) return rc_; }
+        static const int attn_t197 = getenv("SCD_ATTN_T197") ? atoi(getenv("SCD_ATTN_T197")) : 1;   // 0: the generic kernel at T = 197 as well (A/B)
+        if (T == 197 && attn_t197)
+            attention_persist_kernel<true><<<items < 256 ? items : 256, 512, attn_lds, st>>>(qkv, out, T, width, heads, items, attn_xmode());
+        else
+            attention_persist_kernel<false><<<items < 256 ? items : 256, 512, attn_lds, st>>>(qkv, out, T, width, heads, items, attn_xmode());
+    } else if (T == 197) attention_kernel<7><<<items, 256, 0, st>>>(qkv, out, T, width, heads, causal, attn_xmode());
+    else if (T <= 32) {
+        static const int attn_short = getenv("SCD_ATTN_SHORT") ? atoi(getenv("SCD_ATTN_SHORT")) : 1;      // 0: a block per item (attention_kernel<1>; A/B, same bits)
+        if (attn_short) attention_short_kernel<<<(items + 3) / 4, 256, 0, st>>>(qkv, out, T, width, heads, causal, items);
+        else attention_kernel<1><<<items, 256, 0, st>>>(qkv, out, T, width, heads, causal, attn_xmode());
+    }
+    else if (T <= 64) attention_kernel<2><<<items, 256, 0, st>>>(qkv, out, T, width, heads, causal, attn_xmode());
+    else if (T <= 96) attention_kernel<3><<<items, 256, 0, st>>>(qkv, out, T, width, heads, causal, attn_xmode());
+    else SCD_REQUIRE(false, "attention: no kernel for %s T = %d (served: T <= 96, T = 197, non-causal 192 < T <= 224 with SCD_ATTN_PERSIST on)",
+                     causal ? "causal" : "non-causal", T);
+    return SCD_OK;
+}
+
 // LayerNorm folded into the QKV / fc1 GEMMs?  (then the kernel that writes the first block's input also writes its row statistics)
 static bool ln_fused(const scd_encoder* e, const EncPad& pad) {
     static const int ln_fuse_env = getenv("SCD_LN_FUSE") ? atoi(getenv("SCD_LN_FUSE")) : 1;
@@ -1146,25 +1220,8 @@ static int run_blocks(const scd_encoder* e, const EncWs& w, const EncPad& pad, h
                                  d.width, SCD_ACT_NONE, st);
         }
         if (rc) return rc;
-        static const int attn_persist = getenv("SCD_ATTN_PERSIST") ? atoi(getenv("SCD_ATTN_PERSIST")) : 1;
-        if (pad.tokens > 192 && pad.tokens <= 224 && !causal && attn_persist) {
-            constexpr int attn_lds = 2 * 2 * 224 * 128 + 7 * 4096;      // K/V double buffer + the consumers' output patches
-            { const int rc_ = scd_set_max_lds((const void*)attention_persist_kernel<false>, attn_lds); if (rc_) return rc_; }
-            { const int rc_ = scd_set_max_lds((const void*)attention_persist_kernel<true>, attn_lds); if (rc_) return rc_; }
-            const int items = bp * d.heads;
-            static const int attn_t197 = getenv("SCD_ATTN_T197") ? atoi(getenv("SCD_ATTN_T197")) : 1;   // 0: the generic kernel at T = 197 as well (A/B)
-            if (pad.tokens == 197 && attn_t197)
-                attention_persist_kernel<true><<<items < 256 ? items : 256, 512, attn_lds, st>>>(w.qkv, w.y, pad.tokens, d.width, d.heads, items, attn_xmode());
-            else
-                attention_persist_kernel<false><<<items < 256 ? items : 256, 512, attn_lds, st>>>(w.qkv, w.y, pad.tokens, d.width, d.heads, items, attn_xmode());
-        } else if (pad.tokens == 197) attention_kernel<7><<<bp * d.heads, 256, 0, st>>>(w.qkv, w.y, pad.tokens, d.width, d.heads, causal, attn_xmode());
-        else if (pad.tokens <= 32) {
-            static const int attn_short = getenv("SCD_ATTN_SHORT") ? atoi(getenv("SCD_ATTN_SHORT")) : 1;      // 0: a block per item (attention_kernel<1>; A/B, same bits)
-            if (attn_short) attention_short_kernel<<<(bp * d.heads + 3) / 4, 256, 0, st>>>(w.qkv, w.y, pad.tokens, d.width, d.heads, causal, bp * d.heads);
-            else attention_kernel<1><<<bp * d.heads, 256, 0, st>>>(w.qkv, w.y, pad.tokens, d.width, d.heads, causal, attn_xmode());
-        }
-        else if (pad.tokens <= 64) attention_kernel<2><<<bp * d.heads, 256, 0, st>>>(w.qkv, w.y, pad.tokens, d.width, d.heads, causal, attn_xmode());
-        else attention_kernel<3><<<bp * d.heads, 256, 0, st>>>(w.qkv, w.y, pad.tokens, d.width, d.heads, causal, attn_xmode());
+        rc = launch_attention(w.qkv, w.y, bp, pad.tokens, d.width, d.heads, causal, st);
+        if (rc) return rc;
         if (last_sel && l == d.layers - 1) {
             const int bh = pad.bh;
             gather2_rows_kernel<<<(unsigned)scd_cdiv(bh, 4), 256, 0, st>>>(w.y, w.x, w.rows, bh, d.width, w.ysel, w.xsel);
@@ -1345,4 +1402,28 @@ extern "C" int scd_clip_encode_text_len(scd_handle h, const scd_encoder* e, cons
     int rc = run_blocks(e, w, pad, st, &selected);
     if (rc) return rc;
     return run_head(e, w, pad, selected, out, normalize, st);
+}
+
+// ------------------------------------------------------------------------------------------------ attention entry points (tests)
+extern "C" int scd_attention_f16(scd_handle h, const void* qkv, int batch, int T, int width, int heads, int causal, void* out, void* stream) {
+    SCD_DEVICE_ENTRY(h, "scd_attention_f16");
+    SCD_REQUIRE(qkv && out, "scd_attention_f16: null argument");
+    const int rc = launch_attention((const half_t*)qkv, (half_t*)out, batch, T, width, heads, causal != 0, (hipStream_t)stream);
+    if (rc) return rc;
+    SCD_LAUNCH_CHECK();
+    return SCD_OK;
+}
+
+extern "C" int scd_attention_single_query_f16(scd_handle h, const void* kv, const void* q, const int* qrow, int batch, int T, int width,
+                                              int heads, int causal, void* out, void* stream) {
+    SCD_DEVICE_ENTRY(h, "scd_attention_single_query_f16");
+    SCD_REQUIRE(kv && q && out && (qrow || !causal), "scd_attention_single_query_f16: null argument");
+    SCD_REQUIRE(batch > 0 && T > 0 && T <= 256 && heads > 0 && width == heads * 64 && width <= 1024,
+                "scd_attention_single_query_f16: batch %d, T %d (at most 256), width %d / heads %d (head_dim must be 64, width <= 1024)",
+                batch, T, width, heads);
+    const int items = batch * heads;
+    attention_single_query_kernel<<<(unsigned)scd_cdiv(items, 4), 256, 0, (hipStream_t)stream>>>((const half_t*)kv, (const half_t*)q, qrow,
+                                                                                                 (half_t*)out, T, width, heads, items, causal != 0);
+    SCD_LAUNCH_CHECK();
+    return SCD_OK;
 }

@@ -913,6 +913,32 @@ def gemm_f16(a, w, bias=None, residual=None, act=0):
     return c
 
 
+def attention_f16(qkv, batch, T, heads, causal=False):
+    """The encoder blocks' attention (scd_attention_f16): qkv fp16 [batch*T, 3*width] -> out fp16 [batch*T, width]."""
+    _need_cuda(qkv)
+    width = qkv.shape[1] // 3
+    assert qkv.dtype == torch.float16 and qkv.is_contiguous() and qkv.shape == (batch * T, 3 * width)
+    out = torch.empty((batch * T, width), dtype=torch.float16, device=qkv.device)
+    check(_L().scd_attention_f16(handle(), ptr(qkv), int(batch), int(T), width, int(heads), 1 if causal else 0, ptr(out), stream_ptr()))
+    return out
+
+
+def attention_single_query_f16(kv, q, qrow, T, heads, causal=False):
+    """The last block's one-query attention (scd_attention_single_query_f16): kv fp16 [batch*T, 2*width], q fp16 [batch, width],
+    qrow int32 [batch] = b*T + query position (the causal key limit) -> out fp16 [batch, width]."""
+    _need_cuda(kv, q)
+    batch, width = q.shape
+    assert kv.dtype == torch.float16 and q.dtype == torch.float16 and kv.is_contiguous() and q.is_contiguous()
+    assert kv.shape == (batch * T, 2 * width)
+    if qrow is not None:
+        qrow = qrow.to(device=q.device, dtype=torch.int32).contiguous()
+        assert qrow.shape == (batch,)
+    out = torch.empty((batch, width), dtype=torch.float16, device=q.device)
+    check(_L().scd_attention_single_query_f16(handle(), ptr(kv), ptr(q), ptr(qrow), int(batch), int(T), width, int(heads),
+                                              1 if causal else 0, ptr(out), stream_ptr()))
+    return out
+
+
 class Encoder:
     """Owns the device weights (kept alive here) and the scd_encoder handle."""
 
