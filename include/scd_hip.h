@@ -45,6 +45,7 @@ int scd_l2norm_rows(scd_handle h, const void* x, int dtype, int64_t n, int d, vo
 /* ---- similarity + top-k: main_unsup.py:504-531, main_ptsup.py:526-545 (a5); argmax re-classification
  *      main_unsup.py:601-614, main_ptsup.py:668-676, get_clip_preds_fast main_ptsup.py:78-99 (a6).
  * F  [n,d] fp16 row-major (image features);  Wt [v,d] fp16 row-major = zeroshot_weights.T (name-major).
+ * d: a multiple of 64 up to 512 (ViT-B/16: 512), or 768 (ViT-L/14).
  * logits = scale * F @ Wt^T; order = (value desc, index asc) on the exact (float64) dot products.
  * idx_out int64 [n,k]; val_out float32 [n,k] (softmax probability when mode == SCD_SIM_SOFTMAX). k <= 8.
  * fallback_rows_out (device int32, may be NULL) counts rows that took the exact full-row path. */
@@ -381,10 +382,10 @@ int scd_allgather_text(scd_handle h, const void* w_shard, int64_t shard_elems, v
 typedef struct scd_encoder_desc {
     int kind;          /* 0 CLIP visual, 1 CLIP text, 2 DINO/GCD ViT */
     int width, layers, heads, mlp_dim;
-    int tokens;        /* 197 / 77 */
-    int patch, image;  /* 16, 224 (visual) */
+    int tokens;        /* visual: (image/patch)^2 + 1 = 197 (ViT-B/16) or 257 (ViT-L/14); text: 77 */
+    int patch, image;  /* 16 or 14, 224 (visual) */
     int vocab;         /* 49408 (text) */
-    int out_dim;       /* 512 (CLIP) or 0 = no projection (DINO) */
+    int out_dim;       /* 512 (CLIP ViT-B/16), 768 (CLIP ViT-L/14) or 0 = no projection (DINO) */
     int act;           /* 0 QuickGELU, 1 erf GELU */
     float ln_eps;
 } scd_encoder_desc;
@@ -410,8 +411,8 @@ int scd_clip_encode_text_len(scd_handle h, const scd_encoder* e, const int32_t* 
                              int normalize, void* ws, size_t ws_bytes, void* stream);
 /* building block exposed for tests: the encoder blocks' attention, softmax(Q K^T / 8) V per (sequence, head), head_dim 64, width =
  * heads * 64 <= 1024.  qkv fp16 [batch*T][3*width] (Q | K | V, as the QKV GEMM writes them) -> out fp16 [batch*T][width]; causal: query
- * t sees keys 0..t.  Served: T <= 96, T = 197, and non-causal 192 < T <= 224 (SCD_EINVAL otherwise); the kernel is the one the towers
- * run at that T. */
+ * t sees keys 0..t.  Served: T <= 96, T = 197, non-causal 192 < T <= 224 and non-causal 256 < T <= 288 (SCD_EINVAL otherwise); the
+ * kernel is the one the towers run at that T. */
 int scd_attention_f16(scd_handle h, const void* qkv, int batch, int T, int width, int heads, int causal, void* out, void* stream);
 /* building block exposed for tests: the last block's one-query attention (the CLS / EOT row).  kv fp16 [batch*T][2*width] (K | V),
  * q and out fp16 [batch][width], T <= 256; qrow int32 [batch] on the device = b*T + the query's position (causal: the last key it

@@ -32,7 +32,7 @@ def main(argv=None):
     dev = torch.device("cuda")
     if args.synthetic:
         clip.allow_synthetic()
-    model, _ = clip.load("ViT-B/16")
+    model, _ = clip.load(args.clip_model)
     model.cuda().eval()
     k = args.n_cluster
     wn = None
@@ -59,7 +59,7 @@ def main(argv=None):
         data, cdata = mu.extract_or_load_all(args, feat_model, model)
         all_feats, mask_lab, mask_cls, targets = data['all_feats'], data['mask_lab'], data['mask_cls'], data['targets']
         clip_all = torch.as_tensor(cdata['all_feats']).to(dev).half()
-        nouns, zw, wt = mu.load_vocabulary(args, dev)
+        nouns, zw, wt = mu.load_vocabulary(args, dev, model)
         with open(args.class_names) as fh:
             class_to_idx = {kk: int(v) for kk, v in json.load(fh).items()}
         cidx_to_cname = naming.resolve_class_names(args.dataset_name, args.corpus, class_to_idx, nouns, wt, model)
@@ -73,7 +73,7 @@ def main(argv=None):
     mask = np.asarray(mask_cls, dtype=bool)[~mask_lab]
 
     cdir = os.path.join(args.root_dir, 'cluster')
-    cpath = os.path.join(cdir, f'{args.cluster}_{args.feat_model}_{args.dataset_name}.pt')            # :385 (no n_cluster)
+    cpath = os.path.join(cdir, f'{args.cluster}_{mu.feat_cache_name(args)}_{args.dataset_name}.pt')   # :385 (no n_cluster)
     if args.run_cluster or args.synthetic:
         print(f'Fitting {args.cluster} ...')
         all_preds, preds = mu.run_clustering(args, u_feats, l_feats, l_targets)

@@ -8,6 +8,11 @@ Here every stage starts from the reference's own cache files under --root_dir, b
   extracted_features/clip_{dataset}_all.pt           same dict, CLIP features                          (:306-311)
   cluster/{cluster}_{feat_model}_{dataset}_{n_cluster}.pt   dict all_preds, u_preds, u_targets, mask  (:366-374)
   zeroshot_weights/zeroshot_weights_all_{nouns|wikibird|wikidog}_vit_b_16.pt   tensor [512, V]        (:389-394)
+--clip_model picks the CLIP backbone (clip.available_models(), default ViT-B/16: the names above).  With another one every
+CLIP-derived cache carries its tag, so that no cache of one backbone is read as another's features:
+  extracted_features/clip_vit_l_14_{dataset}_all.pt, zeroshot_weights/zeroshot_weights_all_{corpus}_vit_l_14.pt, and
+  clip_vit_l_14 in place of {feat_model} when --feat_model clip.  A missing classifier of such a backbone is built from the corpus
+  (clip_lang_util.zeroshot_classifier, the 80 templates, the backbone's text tower; needs the BPE merges file) and saved.
 The two things the reference takes from its dataset objects are passed as files instead:
   --class_names  JSON {original class name: class index}  (`datasets['test'].class_to_idx` / the sorted breed / wnid tables)
   --images_pt    torch file dict(images [N,3,224,224] preprocessed, targets [N], mask_lab [N]) for --extract_feat true, or
@@ -58,6 +63,7 @@ def build_parser():
     p.add_argument('--cluster_size_max', type=int, default=1200)
     p.add_argument('--corpus', type=str, default='wordnet', help='options: wordnet, wikibird, wikidog')
     p.add_argument('--topk', type=int, default=5)
+    p.add_argument('--clip_model', type=str, default='ViT-B/16', choices=clip.available_models(), help='CLIP backbone')
     p.add_argument('--num_common_vote', type=int, default=20)
     p.add_argument('--num_common_linear', type=int, default=4)
     # additions (see the module docstring)
@@ -112,10 +118,20 @@ def load_or_extract(args, model, feat_model_name, out_name):
     return data
 
 
+def clip_cache_name(args):
+    """'clip' for the default backbone (the reference's cache names), 'clip_vit_l_14' for ViT-L/14."""
+    return 'clip' if args.clip_model == 'ViT-B/16' else 'clip_' + clip.backbone_tag(args.clip_model)
+
+
+def feat_cache_name(args):
+    """{feat_model} of the cache names: tagged with the CLIP backbone when the clustering features are CLIP's."""
+    return clip_cache_name(args) if args.feat_model == 'clip' else args.feat_model
+
+
 def extract_or_load_all(args, feat_model, clip_model):
     """The two feature dicts of :294-313 ({feat_model} and clip).  With --extract_feat true and --image_list: both from ONE pass over
     the image files (scd_amd.images), written to the same cache files as load_or_extract writes; otherwise load_or_extract twice."""
-    fname, cname = f'{args.feat_model}_{args.dataset_name}_all.pt', f'clip_{args.dataset_name}_all.pt'
+    fname, cname = f'{feat_cache_name(args)}_{args.dataset_name}_all.pt', f'{clip_cache_name(args)}_{args.dataset_name}_all.pt'
     if not (args.extract_feat and args.image_list):
         return load_or_extract(args, feat_model, args.feat_model, fname), load_or_extract(args, clip_model, 'clip', cname)
     if args.images_pt:
@@ -143,13 +159,26 @@ def load_feat_model(args, clip_model):
     return DinoViT(torch.load(path, map_location='cpu')).cuda()
 
 
-def load_vocabulary(args, dev):
-    """:381-394: nouns + the [512, V] text classifier."""
-    nouns = [n.lower().replace('-', '_') for n in get_nouns(corpus=args.corpus)]
+def zeroshot_path(args):
     zname = {'wordnet': 'nouns', 'wikibird': 'wikibird', 'wikidog': 'wikidog'}[args.corpus]
+    return os.path.join(args.root_dir, 'zeroshot_weights', f'zeroshot_weights_all_{zname}_{clip.backbone_tag(args.clip_model)}.pt')
+
+
+def load_vocabulary(args, dev, model=None):
+    """:381-394: nouns + the [embed_dim, V] text classifier (built with `model`'s text tower and saved when a non-default backbone
+    has none yet)."""
+    nouns = [n.lower().replace('-', '_') for n in get_nouns(corpus=args.corpus)]
     if args.corpus != 'wordnet':
         nouns = [n.lower().replace("'s", "").replace(' ', '_') for n in nouns]
-    zw = torch.load(os.path.join(args.root_dir, 'zeroshot_weights', f'zeroshot_weights_all_{zname}_vit_b_16.pt'), weights_only=False)
+    path = zeroshot_path(args)
+    if args.clip_model != 'ViT-B/16' and not os.path.exists(path):
+        from local_utils.clip_lang_util import zeroshot_classifier, imagenet_templates
+        print(f"building the {args.clip_model} zero-shot classifier of {len(nouns)} names -> {path}")
+        zw = zeroshot_classifier(nouns, imagenet_templates, model).cpu()
+        os.makedirs(os.path.dirname(path), exist_ok=True)
+        torch.save(zw, path)
+    else:
+        zw = torch.load(path, weights_only=False)
     return nouns, zw, ops.transpose_f16(torch.as_tensor(zw).to(dev).half())
 
 
@@ -171,7 +200,7 @@ def main(argv=None):
     dev = torch.device("cuda")
     if args.synthetic:
         clip.allow_synthetic()
-    model, _ = clip.load("ViT-B/16")
+    model, _ = clip.load(args.clip_model)
     model.cuda().eval()
     wn = None
 
@@ -190,7 +219,7 @@ def main(argv=None):
         data, cdata = extract_or_load_all(args, feat_model, model)
         all_feats, mask_lab, mask_cls, targets = data['all_feats'], data['mask_lab'], data['mask_cls'], data['targets']
         clip_all = torch.as_tensor(cdata['all_feats']).to(dev).half()
-        nouns, zw, wt = load_vocabulary(args, dev)
+        nouns, zw, wt = load_vocabulary(args, dev, model)
         cidx_to_cname = None
         if args.class_names:
             with open(args.class_names) as fh:
@@ -207,7 +236,7 @@ def main(argv=None):
     mask = np.asarray(mask_cls, dtype=bool)[~mask_lab]
 
     cdir = os.path.join(args.root_dir, 'cluster')
-    cpath = os.path.join(cdir, f'{args.cluster}_{args.feat_model}_{args.dataset_name}_{args.n_cluster}.pt')
+    cpath = os.path.join(cdir, f'{args.cluster}_{feat_cache_name(args)}_{args.dataset_name}_{args.n_cluster}.pt')
     if args.run_cluster or args.synthetic:
         print(f'Fitting {args.cluster} ...')
         all_preds, preds = run_clustering(args, u_feats, l_feats, l_targets)

@@ -2,7 +2,7 @@
 
 Mirrors the third-party openai/CLIP package API used by the reference
 (main_unsup.py:237 `clip.load("ViT-B/16")`; clip_lang_util.py:101 `clip.tokenize`).
-Checkpoints: `load` looks for $SCD_ROOT/clip/ViT-B-16.pt - the openai download as it is (a TorchScript archive) or a
+Checkpoints: `load(name)` looks for $SCD_ROOT/clip/<name with '/' -> '-'>.pt (ViT-B-16.pt, ViT-L-14.pt) - the openai download as it is (a TorchScript archive) or a
 torch.save of its state dict.  Without one it RAISES: random-init weights (and the hash tokenizer that stands in for the BPE
 merges file) produce meaningless features, so they must be asked for explicitly - `load(..., synthetic=True)`,
 `clip.allow_synthetic()` or SCD_SYNTHETIC=1 - as bench.py, smoke(), the --synthetic mode of the mains and the tests do
@@ -19,13 +19,19 @@ import torch
 from .model import CLIP, DinoViT
 from . import weights
 
-_MODELS = {"ViT-B/16": weights.CLIP_VITB16}
+_MODELS = {"ViT-B/16": weights.CLIP_VITB16, "ViT-L/14": weights.CLIP_VITL14}
 MEAN = (0.48145466, 0.4578275, 0.40821073)
 STD = (0.26862954, 0.26130258, 0.27577711)
 
 
 def available_models():
     return list(_MODELS)
+
+
+def backbone_tag(name):
+    """'ViT-B/16' -> 'vit_b_16', 'ViT-L/14' -> 'vit_l_14': the suffix of the reference's cache names
+    (zeroshot_weights_all_nouns_vit_b_16.pt)."""
+    return name.lower().replace("/", "_").replace("-", "_")
 
 
 def _preprocess(n_px):
@@ -72,17 +78,19 @@ def load(name="ViT-B/16", device=None, jit=False, download_root=None, seed=0, sy
     if name not in _MODELS:
         raise RuntimeError("Model %s not found; available models = %s" % (name, available_models()))
     root = download_root or os.environ.get("SCD_ROOT", "")
-    path = os.path.join(root, "clip", name.replace("/", "-") + ".pt") if root else ""
+    fname = name.replace("/", "-") + ".pt"
+    path = os.path.join(root, "clip", fname) if root else ""
     if path and os.path.exists(path):
         sd = {k: v for k, v in _read_checkpoint(path).items() if k not in ("input_resolution", "context_length", "vocab_size")}
         synthetic = False
     elif _synthetic_ok(synthetic):
-        sd = weights.synthetic_clip_state_dict(seed=seed)
+        sd = weights.synthetic_clip_state_dict(seed=seed, cfg=_MODELS[name])
         synthetic = True
     else:
-        raise FileNotFoundError("CLIP checkpoint %s not found: put the openai ViT-B-16.pt under $SCD_ROOT/clip/ (or pass "
+        raise FileNotFoundError("CLIP checkpoint %s not found: put the openai %s under $SCD_ROOT/clip/ (or pass "
                                 "download_root); seeded random-init weights must be requested explicitly with "
-                                "load(..., synthetic=True), clip.allow_synthetic() or SCD_SYNTHETIC=1" % (path or "$SCD_ROOT/clip/ViT-B-16.pt"))
+                                "load(..., synthetic=True), clip.allow_synthetic() or SCD_SYNTHETIC=1"
+                                % (path or "$SCD_ROOT/clip/" + fname, fname))
     model = CLIP(sd)
     model.synthetic = synthetic
     if device is None or str(device).startswith("cuda"):

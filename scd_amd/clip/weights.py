@@ -11,6 +11,8 @@ import torch
 
 CLIP_VITB16 = dict(embed_dim=512, image=224, patch=16, v_width=768, v_layers=12, v_heads=12,
                    context=77, vocab=49408, t_width=512, t_layers=12, t_heads=8)
+CLIP_VITL14 = dict(embed_dim=768, image=224, patch=14, v_width=1024, v_layers=24, v_heads=16,
+                   context=77, vocab=49408, t_width=768, t_layers=12, t_heads=12)
 
 
 def _block(sd, g, prefix, width, layers, names):

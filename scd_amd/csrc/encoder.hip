@@ -1,4 +1,4 @@
-// Transformer encoder towers for gfx950: CLIP ViT-B/16 visual and text (third-party `clip`, call sites
+// Transformer encoder towers for gfx950: CLIP ViT-B/16 and ViT-L/14 visual and text (third-party `clip`, call sites
 // /root/reference/main_unsup.py:127 and local_utils/clip_lang_util.py:101-102; structure in SURVEY.md appendix B)
 // and the DINO/GCD ViT-B/16 of /root/reference/gcd/models/vision_transformer.py:135-219.
 //
@@ -23,6 +23,10 @@ struct scd_encoder {
     struct Folded { const half_t *wq, *w1; const float *csq, *bq, *cs1, *b1; };
     std::vector<Folded> folded;
     void* folded_mem = nullptr;
+    // visual towers whose patch GEMM depth 3*P*P is not a multiple of 64 (P = 14: 588): W_PATCH zero-padded to kp columns (640),
+    // owned here; the im2col rows are written at the same padded width
+    int kp = 0;
+    half_t* wpatch_pad = nullptr;
 };
 
 enum { W_PATCH = 0, W_PATCH_B = 1, W_CLS = 2, W_POS = 3, W_LNPRE_W = 4, W_LNPRE_B = 5, W_LNPOST_W = 6, W_LNPOST_B = 7,
@@ -129,6 +133,35 @@ __global__ void __launch_bounds__(256) im2col_kernel(const T* __restrict__ img, 
         for (int q = 0; q < 8; ++q) o[q] = (half_t)0.f;
     }
     *(half8*)(out + e) = o;
+}
+
+// The same matrix for a patch depth kk = 3*P*P that is not a multiple of 64 (P = 14: 588), written at the GEMM's padded row width kp
+// (640): columns kk..kp-1 are zeros, written here (the scratch holds stale data from earlier calls).  One element per thread: with
+// P = 14 eight consecutive columns straddle patch rows.
+template <typename T>
+__global__ void __launch_bounds__(256) im2col_pad_kernel(const T* __restrict__ img, int batch, long long rows_pad, int image, int patch,
+                                                         int kp, half_t* __restrict__ out) {
+    const int gp = image / patch, np = gp * gp, kk = 3 * patch * patch;
+    const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (e >= rows_pad * kp) return;
+    const int col = (int)(e % kp);
+    const long long row = e / kp;
+    const int b = (int)(row / np), p = (int)(row % np);
+    half_t o = (half_t)0.f;
+    if (b < batch && col < kk) {
+        const int c = col / (patch * patch), rem = col % (patch * patch), i = rem / patch, j = rem % patch;
+        const int py = p / gp, px = p % gp;
+        o = (half_t)(float)img[(((size_t)b * 3 + c) * image + (py * patch + i)) * image + px * patch + j];
+    }
+    out[e] = o;
+}
+
+// W [rows][kk] -> Wp [rows][kp], zeros in columns kk..kp-1
+__global__ void __launch_bounds__(256) pad_cols_kernel(const half_t* __restrict__ w, long long rows, int kk, int kp, half_t* __restrict__ wp) {
+    const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (e >= rows * kp) return;
+    const int col = (int)(e % kp);
+    wp[e] = col < kk ? w[(e / kp) * kk + col] : (half_t)0.f;
 }
 
 // token assembly (+ optional ln_pre): x[b][0] = cls + pos[0]; x[b][1+p] = patch[b*np+p] + patch_bias + pos[1+p]
@@ -376,8 +409,13 @@ __device__ __forceinline__ bool max_offset_is_large(float mx, float cs, float mx
     return __builtin_amdgcn_ballot_w64(fabsf(fmaf(mx, cs, -mxs)) > 0.5f) != 0;
 }
 
-template <int NB>   // NB = ceil(T/32): 7 for T=197, 3 for T=77
-__global__ void __launch_bounds__(256, 2) attention_kernel(const half_t* __restrict__ qkv, half_t* __restrict__ out, int T, int width,
+// NB = 9 (non-causal 256 < T <= 288, the ViT-L/14 towers at T = 257): one block per CU.  At two blocks per CU (256 registers per
+// lane) hipcc spills 70-84 VGPRs to scratch; at one it keeps everything in the 512 VGPRs + AGPRs of a wave alone on its SIMD, and the
+// 92 KB of K and V fit beside nothing else anyway.  ONE_KEY (T = 257): of the last key block only key 256 is valid, so 12 of its 16
+// exponentials per lane and its second pair of P V MFMAs (keys 272..287) are not executed (their probabilities are exactly 0: the
+// same bits, as attention_persist_kernel<true>).
+template <int NB, bool ONE_KEY = false>   // NB = ceil(T/32): 7 for T=197, 3 for T=77, 9 for T=257
+__global__ void __launch_bounds__(256, NB > 7 ? 1 : 2) attention_kernel(const half_t* __restrict__ qkv, half_t* __restrict__ out, int T, int width,
                                                            int heads, int causal, int xmode) {
     constexpr int TP = NB * 32;
     constexpr int VS = 192;                          // V row stride in bytes: 4 rows x 64 B of a tr-read tile the 64 banks
@@ -443,7 +481,7 @@ __global__ void __launch_bounds__(256, 2) attention_kernel(const half_t* __restr
 #pragma unroll
         for (int kb = 0; kb < NB; ++kb)
 #pragma unroll
-            for (int i = 0; i < 16; ++i) {
+            for (int i = 0; i < (ONE_KEY && kb == NB - 1 ? 4 : 16); ++i) {   // ONE_KEY: registers 4..15 of the last block hold keys >= 264
                 float v = sacc[kb][i];
                 if (kb == NB - 1 || causal) {
                     const int key = kb * 32 + (i & 3) + 8 * (i >> 2) + 4 * hh;
@@ -460,7 +498,7 @@ __global__ void __launch_bounds__(256, 2) attention_kernel(const half_t* __restr
 #pragma unroll
             for (int kb = 0; kb < NB; ++kb)
 #pragma unroll
-                for (int i = 0; i < 16; ++i) sacc[kb][i] = fmaf(sacc[kb][i], cs, -mxs) - off;
+                for (int i = 0; i < (ONE_KEY && kb == NB - 1 ? 4 : 16); ++i) sacc[kb][i] = fmaf(sacc[kb][i], cs, -mxs) - off;
             cs = 1.f;
             mxs = 0.f;
         }
@@ -469,6 +507,7 @@ __global__ void __launch_bounds__(256, 2) attention_kernel(const half_t* __restr
         for (int kb = 0; kb < NB; ++kb)
 #pragma unroll
             for (int i = 0; i < 16; ++i) {
+                if (ONE_KEY && kb == NB - 1 && i >= 4) { sacc[kb][i] = 0.f; continue; }   // key >= 264: p = 0
                 const float p = __builtin_amdgcn_exp2f(fmaf(sacc[kb][i], cs, -mxs));
                 sacc[kb][i] = p;
                 sum += p;
@@ -484,7 +523,7 @@ __global__ void __launch_bounds__(256, 2) attention_kernel(const half_t* __restr
         for (int kb = 0; kb < NB; ++kb) {
             if (xmode & 2) break;
 #pragma unroll
-            for (int s = 0; s < 2; ++s) {
+            for (int s = 0; s < (ONE_KEY && kb == NB - 1 ? 1 : 2); ++s) {   // ONE_KEY: keys 272..287 contribute exactly nothing
                 half8 pf;
 #pragma unroll
                 for (int j = 0; j < 8; ++j) pf[j] = (half_t)sacc[kb][8 * s + j];
@@ -1037,9 +1076,11 @@ extern "C" int scd_encoder_create(scd_handle h, const scd_encoder_desc* desc, co
         SCD_REQUIRE(weights[W_PATCH] && weights[W_POS] && weights[W_LNPOST_W] && weights[W_LNPOST_B] && weights[W_PROJ] && d.out_dim > 0,
                     "scd_encoder_create: text tower weight missing");
     } else {
-        SCD_REQUIRE(d.patch > 0 && d.image % d.patch == 0 && (3 * d.patch * d.patch) % 64 == 0, "scd_encoder_create: bad patch/image");
+        SCD_REQUIRE(d.patch > 0 && d.image % d.patch == 0 && scd_cdiv(3 * d.patch * d.patch, 64) * 64 <= 3 * d.width,
+                    "scd_encoder_create: bad patch/image");
         const int np = (d.image / d.patch) * (d.image / d.patch);
-        SCD_REQUIRE(d.tokens == np + 1 && d.tokens == 197, "scd_encoder_create: visual tower expects 197 tokens, got %d", d.tokens);
+        SCD_REQUIRE(d.tokens == np + 1 && (d.tokens == 197 || d.tokens == 257),
+                    "scd_encoder_create: visual tower expects (image/patch)^2 + 1 = 197 or 257 tokens, got %d", d.tokens);
         SCD_REQUIRE(weights[W_PATCH] && weights[W_CLS] && weights[W_POS] && weights[W_LNPOST_W] && weights[W_LNPOST_B],
                     "scd_encoder_create: visual tower weight missing");
         SCD_REQUIRE((d.out_dim > 0) == (weights[W_PROJ] != nullptr), "scd_encoder_create: projection / out_dim mismatch");
@@ -1050,6 +1091,17 @@ extern "C" int scd_encoder_create(scd_handle h, const scd_encoder_desc* desc, co
     scd_encoder* e = new scd_encoder();
     e->d = d;
     e->w.assign(weights, weights + n_weights);
+    if (d.kind != 1 && (3 * d.patch * d.patch) % 64 != 0) {
+        const int kk = 3 * d.patch * d.patch;
+        e->kp = (int)scd_cdiv(kk, 64) * 64;
+        const long long n = (long long)d.width * e->kp;
+        if (hipMalloc(&e->wpatch_pad, (size_t)n * 2) != hipSuccess) {
+            delete e;
+            SCD_REQUIRE(false, "scd_encoder_create: out of device memory for the padded patch weight");
+        }
+        pad_cols_kernel<<<(unsigned)scd_cdiv(n, 256), 256>>>((const half_t*)weights[W_PATCH], d.width, kk, e->kp, e->wpatch_pad);
+        SCD_HIP(hipDeviceSynchronize());
+    }
     // fold LN1 into the QKV weights and LN2 into the fc1 weights (used when every GEMM of a block can take the four-wave
     // kernel: widths multiples of 256)
     if (d.width % 256 == 0 && d.mlp_dim % 256 == 0) {
@@ -1081,6 +1133,7 @@ extern "C" int scd_encoder_create(scd_handle h, const scd_encoder_desc* desc, co
 
 extern "C" int scd_encoder_destroy(scd_encoder* e) {
     if (e && e->folded_mem) hipFree(e->folded_mem);
+    if (e && e->wpatch_pad) hipFree(e->wpatch_pad);
     delete e;
     return SCD_OK;
 }
@@ -1117,7 +1170,8 @@ static int attn_xmode() {
 
 // The attention of every block (run_blocks) and of scd_attention_f16: qkv [batch*T][3*width] (Q | K | V, heads in 64-wide slices, as the
 // QKV GEMM writes them) -> out [batch*T][width].  The kernel is chosen by T: attention_short_kernel (T <= 32), attention_kernel<2> / <3>
-// (T <= 64 / 96), attention_persist_kernel (non-causal 192 < T <= 224; <true> at T = 197), attention_kernel<7> (T = 197 otherwise).
+// (T <= 64 / 96), attention_persist_kernel (non-causal 192 < T <= 224; <true> at T = 197), attention_kernel<7> (T = 197 otherwise),
+// attention_kernel<9> (non-causal 256 < T <= 288; <9, true> at T = 257, ViT-L/14).
 // attention_kernel<NB> stages 32*NB keys and computes 32*NB queries, so every other (T, causal) is refused rather than launched.
 static int launch_attention(const half_t* qkv, half_t* out, int batch, int T, int width, int heads, int causal, hipStream_t st) {
     SCD_REQUIRE(batch > 0 && T > 0 && heads > 0 && width == heads * 64 && width <= 1024,
@@ -1134,6 +1188,10 @@ static int launch_attention(const half_t* qkv, half_t* out, int batch, int T, in
         else
             attention_persist_kernel<false><<<items < 256 ? items : 256, 512, attn_lds, st>>>(qkv, out, T, width, heads, items, attn_xmode());
     } else if (T == 197) attention_kernel<7><<<items, 256, 0, st>>>(qkv, out, T, width, heads, causal, attn_xmode());
+    else if (T > 256 && T <= 288 && !causal) {
+        if (T == 257) attention_kernel<9, true><<<items, 256, 0, st>>>(qkv, out, T, width, heads, causal, attn_xmode());
+        else attention_kernel<9><<<items, 256, 0, st>>>(qkv, out, T, width, heads, causal, attn_xmode());
+    }
     else if (T <= 32) {
         static const int attn_short = getenv("SCD_ATTN_SHORT") ? atoi(getenv("SCD_ATTN_SHORT")) : 1;      // 0: a block per item (attention_kernel<1>; A/B, same bits)
         if (attn_short) attention_short_kernel<<<(items + 3) / 4, 256, 0, st>>>(qkv, out, T, width, heads, causal, items);
@@ -1141,7 +1199,8 @@ static int launch_attention(const half_t* qkv, half_t* out, int batch, int T, in
     }
     else if (T <= 64) attention_kernel<2><<<items, 256, 0, st>>>(qkv, out, T, width, heads, causal, attn_xmode());
     else if (T <= 96) attention_kernel<3><<<items, 256, 0, st>>>(qkv, out, T, width, heads, causal, attn_xmode());
-    else SCD_REQUIRE(false, "attention: no kernel for %s T = %d (served: T <= 96, T = 197, non-causal 192 < T <= 224 with SCD_ATTN_PERSIST on)",
+    else SCD_REQUIRE(false, "attention: no kernel for %s T = %d (served: T <= 96, T = 197, non-causal 192 < T <= 224 with SCD_ATTN_PERSIST on, "
+                            "non-causal 256 < T <= 288)",
                      causal ? "causal" : "non-causal", T);
     return SCD_OK;
 }
@@ -1327,7 +1386,7 @@ extern "C" int scd_vit_encode_image(scd_handle h, const scd_encoder* e, const vo
     const scd_encoder_desc& d = e->d;
     const EncPad pad = make_pad(d, batch);
     EncWs w = carve(d, pad, (char*)ws);
-    const int kk = 3 * d.patch * d.patch;
+    const int kk = e->kp > 0 ? e->kp : 3 * d.patch * d.patch;    // GEMM depth: 3*P*P, or its padded width (P = 14)
     const long long total8 = pad.prows * kk / 8;
     half_t* cols = w.qkv;      // [prows, kk] scratch (fits: kk <= 3*width, prows <= rows)
     SCD_REQUIRE(kk <= 3 * d.width, "scd_vit_encode_image: patch too large for scratch");
@@ -1339,6 +1398,11 @@ extern "C" int scd_vit_encode_image(scd_handle h, const scd_encoder* e, const vo
                             (double)batch * 3.0 * d.image * d.image * 2.0 < 4294967296.0;
     if (from_image) {
         rc = scd_gemm_launch_img((const half_t*)pixels, (const half_t*)e->w[W_PATCH], w.y, pad.prows, d.width, batch, d.image, st);
+    } else if (e->kp > 0) {
+        const long long total = pad.prows * kk;
+        if (dtype == SCD_F32) im2col_pad_kernel<float><<<(unsigned)scd_cdiv(total, 256), 256, 0, st>>>((const float*)pixels, batch, pad.prows, d.image, d.patch, kk, cols);
+        else im2col_pad_kernel<half_t><<<(unsigned)scd_cdiv(total, 256), 256, 0, st>>>((const half_t*)pixels, batch, pad.prows, d.image, d.patch, kk, cols);
+        rc = scd_gemm_launch(cols, e->wpatch_pad, nullptr, nullptr, w.y, pad.prows, d.width, kk, SCD_ACT_NONE, st);
     } else {
         if (dtype == SCD_F32) im2col_kernel<float><<<(unsigned)scd_cdiv(total8, 256), 256, 0, st>>>((const float*)pixels, batch, pad.prows, d.image, d.patch, cols);
         else im2col_kernel<half_t><<<(unsigned)scd_cdiv(total8, 256), 256, 0, st>>>((const half_t*)pixels, batch, pad.prows, d.image, d.patch, cols);

@@ -74,8 +74,10 @@ typedef __attribute__((address_space(3))) void* sim_lds_ptr_t;
 // NW = 8 (default): one 512-thread block (256 images) per CU.  NW = 4 (SCD_SIM_NW=4, same speed): TWO independent 256-thread blocks (128 images each)
 // per CU: their tile epilogues (the divergent top-8 maintenance, ~1/3 of the kernel) drift apart, so one block's MFMAs run
 // under the other's epilogue - with eight waves behind one barrier all of them reach the epilogue together.
-template <bool SOFTMAX, int NW>
-__global__ void __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) sim_topk_kernel(const half_t* __restrict__ F, const half_t* __restrict__ Wt,
+// NDC = 12 (d = 768, the ViT-L/14 embedding; NW = 4): 44 of the 48 image fragments in registers, which takes the register file of a
+// wave that is alone on its SIMD (512 registers): one 256-thread block (128 images) per CU.
+template <bool SOFTMAX, int NW, int NDC = 8>
+__global__ void __launch_bounds__(NW * 64, NW == 4 && NDC == 8 ? 2 : 1) sim_topk_kernel(const half_t* __restrict__ F, const half_t* __restrict__ Wt,
                                                           long long n, int d, long long v, float scale,
                                                           float* __restrict__ cand_val, int* __restrict__ cand_idx,
                                                           float* __restrict__ stats, int xmode) {
@@ -91,10 +93,11 @@ __global__ void __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) sim_topk_kernel(cons
     // 28 of the 32 image fragments stay in registers; the last four (d-chunk 7) are parked in a per-wave LDS
     // patch and re-read once per tile: with all 32 resident hipcc spills some of them to scratch, and every scratch reload
     // is a vmcnt(0) that drains the fill ring
-    half8 bf[28];
+    constexpr int NBF = 4 * NDC - 4;                                 // fragments in registers; d-chunk NDC - 1 is parked
+    half8 bf[NBF];
     char* bfl = smem + 65536 + wave * 4096 + lane * 16;
 #pragma unroll
-    for (int s = 0; s < 32; ++s) {
+    for (int s = 0; s < 4 * NDC; ++s) {
         half8 t;
         if (16 * s < d) {
             t = *(const half8*)(frow + 16 * s);
@@ -102,13 +105,13 @@ __global__ void __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) sim_topk_kernel(cons
 #pragma unroll
             for (int q = 0; q < 8; ++q) t[q] = (half_t)0.f;
         }
-        if (s < 28) bf[s] = t;
-        else *(half8*)(bfl + (s - 28) * 1024) = t;
+        if (s < NBF) bf[s] = t;
+        else *(half8*)(bfl + (s - NBF) * 1024) = t;
     }
     // the image fragments are complete before the loop: a load still pending at the loop header makes hipcc put a
     // vmcnt(0) in front of the first use of every fragment in every sub-step, which drains the fill ring each time
 #pragma unroll
-    for (int s = 0; s < 28; ++s) asm volatile("" : "+v"(bf[s]));
+    for (int s = 0; s < NBF; ++s) asm volatile("" : "+v"(bf[s]));
     float lv[TOPM];
     int li[TOPM];
 #pragma unroll
@@ -183,16 +186,16 @@ __global__ void __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) sim_topk_kernel(cons
     int s = 0;                                              // flattened sub-step counter (ring slot = s & 3)
     for (int tile = 0; tile < ntiles; ++tile) {
 #pragma unroll
-        for (int dcc = 0; dcc < 8; ++dcc) {                 // d-chunk index is a compile-time constant: bf[] stays in registers
+        for (int dcc = 0; dcc < NDC; ++dcc) {               // d-chunk index is a compile-time constant: bf[] stays in registers
             if (dcc < nd) {
                 const char* cur = smem + (s & 3) * 16384;
                 half8 b0, b1, b2, b3;
-                if (dcc == 7) {
+                if (dcc == NDC - 1) {
                     b0 = *(const half8*)bfl; b1 = *(const half8*)(bfl + 1024);
                     b2 = *(const half8*)(bfl + 2048); b3 = *(const half8*)(bfl + 3072);
                 } else {
-                    b0 = bf[(dcc & 7) * 4 + 0 < 28 ? dcc * 4 + 0 : 0]; b1 = bf[dcc * 4 + 1 < 28 ? dcc * 4 + 1 : 0];
-                    b2 = bf[dcc * 4 + 2 < 28 ? dcc * 4 + 2 : 0]; b3 = bf[dcc * 4 + 3 < 28 ? dcc * 4 + 3 : 0];
+                    b0 = bf[dcc * 4 + 0 < NBF ? dcc * 4 + 0 : 0]; b1 = bf[dcc * 4 + 1 < NBF ? dcc * 4 + 1 : 0];
+                    b2 = bf[dcc * 4 + 2 < NBF ? dcc * 4 + 2 : 0]; b3 = bf[dcc * 4 + 3 < NBF ? dcc * 4 + 3 : 0];
                 }
                 rd(cur, 1, fb);
                 mm(fa, b0);
@@ -1886,10 +1889,13 @@ __global__ void __launch_bounds__(256) sim_exact_merge_kernel(const SimHdr* hdr,
 template <bool SOFTMAX>
 static int sim_exact_launch(const half_t* f, const half_t* wt, int d, long long v, float scale, int k, const SimHdr* hdr, const int* fb,
                             ExPart* part, long long* idx_out, float* val_out, hipStream_t st) {
-    const int nch = ex_nchunks(v), cap = ex_rows_cap(v);
-    { const int rc_ = scd_set_max_lds((const void*)sim_exact_chunk_kernel<SOFTMAX>, EX_LDS); if (rc_) return rc_; }
-    sim_exact_chunk_kernel<SOFTMAX><<<nch, 256, EX_LDS, st>>>(f, wt, d, v, scale, hdr, fb, part, cap, nch);
-    sim_exact_merge_kernel<SOFTMAX><<<cap, 256, 0, st>>>(hdr, fb, part, k, idx_out, val_out, cap, nch);
+    // the chunk kernels stage rows of at most 512 d (EX_LDW); wider rows (d = 768) all take the one-block-per-row kernel
+    const int nch = ex_nchunks(v), cap = d <= 512 ? ex_rows_cap(v) : 0;
+    if (cap > 0) {
+        { const int rc_ = scd_set_max_lds((const void*)sim_exact_chunk_kernel<SOFTMAX>, EX_LDS); if (rc_) return rc_; }
+        sim_exact_chunk_kernel<SOFTMAX><<<nch, 256, EX_LDS, st>>>(f, wt, d, v, scale, hdr, fb, part, cap, nch);
+        sim_exact_merge_kernel<SOFTMAX><<<cap, 256, 0, st>>>(hdr, fb, part, k, idx_out, val_out, cap, nch);
+    }
     sim_exact_kernel<SOFTMAX><<<256, 256, 0, st>>>(f, wt, d, v, scale, k, hdr, fb, idx_out, val_out, cap);
     return SCD_OK;
 }
@@ -1934,7 +1940,7 @@ static int sim_topk_impl(scd_handle h, const void* F, const void* Wt, int64_t n,
                          size_t ws_bytes, const void* wmax2, void* stream_) {
     SCD_REQUIRE(h && F && Wt && idx_out && val_out && ws, "scd_sim_topk: null argument");
     SCD_REQUIRE(n > 0 && v > 0 && n < (1ll << 31) && v < (1ll << 31), "scd_sim_topk: bad shape n=%lld v=%lld", (long long)n, (long long)v);
-    SCD_REQUIRE(d > 0 && d <= 512 && d % 64 == 0, "scd_sim_topk: d=%d must be a multiple of 64, <= 512", d);
+    SCD_REQUIRE(d > 0 && (d <= 512 || d == 768) && d % 64 == 0, "scd_sim_topk: d=%d must be a multiple of 64 up to 512, or 768", d);
     SCD_REQUIRE(k >= 1 && k <= TOPM && k <= v, "scd_sim_topk: k=%d must be in [1,%d] and <= v", k, TOPM);
     SCD_REQUIRE(mode == SCD_SIM_RAW || mode == SCD_SIM_SOFTMAX, "scd_sim_topk: bad mode %d", mode);
     SCD_REQUIRE(scale > 0.f, "scd_sim_topk: scale must be positive");
@@ -2064,6 +2070,24 @@ static int sim_topk_impl(scd_handle h, const void* F, const void* Wt, int64_t n,
 #undef RB8_GO
 #undef RC_GO
 #undef RB_TAIL
+        if (fallback_rows_out) SCD_HIP(hipMemcpyAsync(fallback_rows_out, &hdr->fb_cnt, 4, hipMemcpyDeviceToDevice, st));
+        SCD_LAUNCH_CHECK();
+        return SCD_OK;
+    }
+    if (d == 768) {
+        // the ViT-L/14 width: the four-wave tile kernel with twelve 64-deep sub-steps per tile (128 images x 128 names)
+        const unsigned g4 = (unsigned)scd_cdiv(n, 128);
+        { const int rc_ = scd_set_max_lds((const void*)sim_topk_kernel<true, 4, 12>, 65536 + 16384); if (rc_) return rc_; }
+        { const int rc_ = scd_set_max_lds((const void*)sim_topk_kernel<false, 4, 12>, 65536 + 16384); if (rc_) return rc_; }
+        if (sm) {
+            sim_topk_kernel<true, 4, 12><<<g4, 256, 65536 + 16384, st>>>(f, wt, n, d, v, scale, cval, cidx, stats, 0);
+            sim_refine_kernel<true, TOPM><<<g2, 256, 0, st>>>(f, wt, n, d, v, scale, k, cval, cidx, stats, hdr, fb, (long long*)idx_out, val_out, -1);
+            { const int rc_ = sim_exact_launch<true>(f, wt, d, v, scale, k, hdr, fb, expart, (long long*)idx_out, val_out, st); if (rc_) return rc_; }
+        } else {
+            sim_topk_kernel<false, 4, 12><<<g4, 256, 65536 + 16384, st>>>(f, wt, n, d, v, scale, cval, cidx, stats, 0);
+            sim_refine_kernel<false, TOPM><<<g2, 256, 0, st>>>(f, wt, n, d, v, scale, k, cval, cidx, stats, hdr, fb, (long long*)idx_out, val_out, -1);
+            { const int rc_ = sim_exact_launch<false>(f, wt, d, v, scale, k, hdr, fb, expart, (long long*)idx_out, val_out, st); if (rc_) return rc_; }
+        }
         if (fallback_rows_out) SCD_HIP(hipMemcpyAsync(fallback_rows_out, &hdr->fb_cnt, 4, hipMemcpyDeviceToDevice, st));
         SCD_LAUNCH_CHECK();
         return SCD_OK;

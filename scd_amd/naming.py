@@ -67,7 +67,7 @@ def _first_index(nouns):
 def vote_loop_unsup(name_idx, u_preds, clip_u_feats, wt, nouns, n_cluster, num_common_vote, num_common_linear,
                     on_iter=None, max_iter=1000):
     """main_unsup.py:568-614.  name_idx int64 [N_u, TOP_K] (device), u_preds int64 [N_u] (device or numpy),
-    wt = zeroshot_weights.T fp16 [V, 512] (device).  Returns (cand_names, u_preds numpy, trace)."""
+    wt = zeroshot_weights.T fp16 [V, d] (d = the CLIP embedding width: 512 for ViT-B/16, 768 for ViT-L/14) (device).  Returns (cand_names, u_preds numpy, trace)."""
     dev = name_idx.device
     u_preds = torch.as_tensor(u_preds, dtype=torch.int64, device=dev)
     first = _first_index(nouns)
@@ -165,15 +165,15 @@ def match_missing_names(miss_names, nouns, wt, model, mode="top1", nouns_truncat
     mode "top1", nouns_truncated given  main_unsup.py:487-491 (cub): top-1 over the names that are not class names
     mode "greedy_top5"                  main_unsup.py:459-469 (sdogs + wikidog): top-5 over nouns_truncated, each class takes
                                         its best name that no earlier class has taken
-    (the same code at main_ptsup.py:419-423, 477-487, 505-509).  wt = zeroshot_weights.T [V,512] fp16 on the device;
+    (the same code at main_ptsup.py:419-423, 477-487, 505-509).  wt = zeroshot_weights.T [V, d] fp16 on the device;
     the text classifier of the missing names is built by zeroshot_classifier on the HIP text tower unless `miss_weights`
-    ([512, m]) is given.  Returns the list of matched names, one per missing name."""
+    ([d, m]) is given.  Returns the list of matched names, one per missing name."""
     if len(miss_names) == 0:
         return []
     if miss_weights is None:
         from .local_utils.clip_lang_util import imagenet_templates, zeroshot_classifier
         miss_weights = zeroshot_classifier(list(miss_names), templates or imagenet_templates, model)
-    f = miss_weights.t().contiguous().to(device=wt.device, dtype=torch.float16)                  # [m, 512]
+    f = miss_weights.t().contiguous().to(device=wt.device, dtype=torch.float16)                  # [m, d]
     if nouns_truncated is None:
         pool, w_pool = nouns, wt
     else:
@@ -227,7 +227,7 @@ def resolve_class_names(dataset_name, corpus, class_to_idx, nouns, wt, model):
 
 # ----------------------------------------------------------------------------- zero-shot bounds of main_ptsup.py
 def _as_wt(zeroshot_weights):
-    """[512, V] classifier (any float dtype, host or device) -> name-major fp16 [V, 512] on the device."""
+    """[d, V] classifier (any float dtype, host or device) -> name-major fp16 [V, d] on the device."""
     w = torch.as_tensor(zeroshot_weights)
     if not w.is_cuda:
         w = w.cuda()
@@ -253,7 +253,7 @@ def get_clip_preds_fast(clip_feats, targets, cidx_to_cname, nouns, zeroshot_weig
 
 
 def evaluate_semantic_acc_ub_lb(clip_feats, targets, cidx_to_cname, nouns, zeroshot_weights, return_top5=False):
-    """main_ptsup.py:102-129: top-1 accuracy (%) of the zero-shot classifier `zeroshot_weights` ([512, len(nouns)]) against
+    """main_ptsup.py:102-129: top-1 accuracy (%) of the zero-shot classifier `zeroshot_weights` ([d, len(nouns)]) against
     the vocabulary index of each row's class name - the lower bound with the full vocabulary, the upper bound with the
     ground-truth names only (call sites :550-561)."""
     first = _first_index(nouns)

@@ -32,7 +32,7 @@ def run(model, images, mask_lab, l_targets, wt, nouns, n_cluster, topk=3, num_co
     """One pass over `images` (this rank's shard).  Returns dict(feats, labels, cand_names, u_preds, name_idx).
     build_vocab: a callable returning the name-major classifier W^T - the open-vocabulary build of BASELINE configs[4] (text tower over
     the names, clip_lang_util.zeroshot_classifier[_sharded]) then runs INSIDE the pass ("text_tower" stage) instead of `wt` being
-    handed in.  text_feats [n, 512] fp16: per-image closed-set text features for the textual-enhancement re-ranking - top-k and the vote
+    handed in.  text_feats [n, d] fp16: per-image closed-set text features for the textual-enhancement re-ranking - top-k and the vote
     loop's re-classification then use 100 * (f @ W + t @ W) / 2 = 100 * mean(f, t) @ W (the formula the reference keeps commented at
     main_unsup.py:518,523,604,609); the clustering still sees the image features."""
     def mark(name):
@@ -95,7 +95,7 @@ def run_cached(cluster_feats, clip_feats, mask_lab, wt, nouns, n_cluster, topk=3
     """The pass of BASELINE configs[0] (CUB-200 unsupervised on cached features, main_unsup.py:298-364 with `extract_feature` replaced
     by the cache files it writes): no encoder at all - full-vocabulary top-k of the cached CLIP features, the clustering of the cached
     DINO features' unlabelled rows (`--cluster KM`, the shipped flag: `KMeans(n_clusters, random_state=0).fit(u_feats)`, :362; or SSKM)
-    and the vote loop (:568-614).  cluster_feats float32 [n, 768], clip_feats fp16 [n, 512], both resident in HBM."""
+    and the vote loop (:568-614).  cluster_feats float32 [n, 768], clip_feats fp16 [n, d] (d = the CLIP embedding width), both resident in HBM."""
     def mark(name):
         if timers is not None:
             ev = torch.cuda.Event(enable_timing=True)
@@ -286,7 +286,7 @@ def synthetic_images(n, n_classes, seed, device, noise=0.35, chunk=4096, dtype=t
 
 
 def synthetic_vocab(model, base, v, seed, device, jitter=0.05):
-    """W^T [v,512] fp16: row c < K is the (jittered) CLIP feature of class c's base image (the 'true' name), the rest
+    """W^T [v, d] fp16: row c < K is the (jittered) CLIP feature of class c's base image (the 'true' name), the rest
     are random unit vectors.  Returns (wt, nouns)."""
     protos = model.visual.enc.encode_image(base.to(torch.float16), normalize=True).float()
     g = torch.Generator(device=device).manual_seed(7 + seed)
