@@ -68,16 +68,6 @@ int scd_check_device(const struct scd_ctx* h, const char* who);
         if (rc_dev_) return rc_dev_;                            \
     } while (0)
 
-// Environment switches that can change RESULTS (timing ablations: kernels with pieces removed) or that select kernels kept only for
-// A/B measurements exist in builds with -DSCD_ABLATE (`python -m scd_amd.build --ablate` -> lib/libscd_hip_ablate.so, loaded through
-// SCD_HIP_LIB).  The default library does not read these variables and does not contain the code behind them.
-#ifdef SCD_ABLATE
-#include <stdlib.h>
-#define SCD_ABLATE_ENV(name, dflt) (getenv(name) ? atoi(getenv(name)) : (dflt))
-#else
-#define SCD_ABLATE_ENV(name, dflt) (dflt)
-#endif
-
 typedef _Float16 half_t;
 typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 typedef _Float16 half4 __attribute__((ext_vector_type(4)));

@@ -416,7 +416,7 @@ __device__ __forceinline__ bool max_offset_is_large(float mx, float cs, float mx
 // same bits, as attention_persist_kernel<true>).
 template <int NB, bool ONE_KEY = false>   // NB = ceil(T/32): 7 for T=197, 3 for T=77, 9 for T=257
 __global__ void __launch_bounds__(256, NB > 7 ? 1 : 2) attention_kernel(const half_t* __restrict__ qkv, half_t* __restrict__ out, int T, int width,
-                                                           int heads, int causal, int xmode) {
+                                                           int heads, int causal, int xmode) {   // xmode: always 0; without it <9> spills
     constexpr int TP = NB * 32;
     constexpr int VS = 192;                          // V row stride in bytes: 4 rows x 64 B of a tr-read tile the 64 banks
     __shared__ __attribute__((aligned(16))) char kl[TP * 128];
@@ -694,7 +694,7 @@ __global__ void __launch_bounds__(256) attention_short_kernel(const half_t* __re
 // starts at +0: the same bits).  The K rows that are not filled hold whatever the LDS held; their scores are never read.
 template <bool T197>
 __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2)))
-attention_persist_kernel(const half_t* __restrict__ qkv, half_t* __restrict__ out, int T, int width, int heads, int items, int xmode) {
+attention_persist_kernel(const half_t* __restrict__ qkv, half_t* __restrict__ out, int T, int width, int heads, int items, int xmode) {   // xmode: always 0; kept, see gemm_w4_kernel
     constexpr int NB = 7, TP = NB * 32, KV = TP * 128;
     extern __shared__ __attribute__((aligned(16))) char smem[];   // [2][K | V]
     const int tid = threadIdx.x, lane = tid & 63;
@@ -1163,11 +1163,6 @@ extern "C" size_t scd_encoder_ws_bytes(const scd_encoder* e, int batch) {
     return carve(e->d, make_pad(e->d, batch), nullptr).total;
 }
 
-static int attn_xmode() {
-    static const int x = SCD_ABLATE_ENV("SCD_ATTN_X", 0);   // timing ablations only
-    return x;
-}
-
 // The attention of every block (run_blocks) and of scd_attention_f16: qkv [batch*T][3*width] (Q | K | V, heads in 64-wide slices, as the
 // QKV GEMM writes them) -> out [batch*T][width].  The kernel is chosen by T: attention_short_kernel (T <= 32), attention_kernel<2> / <3>
 // (T <= 64 / 96), attention_persist_kernel (non-causal 192 < T <= 224; <true> at T = 197), attention_kernel<7> (T = 197 otherwise),
@@ -1184,21 +1179,21 @@ static int launch_attention(const half_t* qkv, half_t* out, int batch, int T, in
         { const int rc_ = scd_set_max_lds((const void*)attention_persist_kernel<true>, attn_lds); if (rc_) return rc_; }
         static const int attn_t197 = getenv("SCD_ATTN_T197") ? atoi(getenv("SCD_ATTN_T197")) : 1;   // 0: the generic kernel at T = 197 as well (A/B)
         if (T == 197 && attn_t197)
-            attention_persist_kernel<true><<<items < 256 ? items : 256, 512, attn_lds, st>>>(qkv, out, T, width, heads, items, attn_xmode());
+            attention_persist_kernel<true><<<items < 256 ? items : 256, 512, attn_lds, st>>>(qkv, out, T, width, heads, items, 0);
         else
-            attention_persist_kernel<false><<<items < 256 ? items : 256, 512, attn_lds, st>>>(qkv, out, T, width, heads, items, attn_xmode());
-    } else if (T == 197) attention_kernel<7><<<items, 256, 0, st>>>(qkv, out, T, width, heads, causal, attn_xmode());
+            attention_persist_kernel<false><<<items < 256 ? items : 256, 512, attn_lds, st>>>(qkv, out, T, width, heads, items, 0);
+    } else if (T == 197) attention_kernel<7><<<items, 256, 0, st>>>(qkv, out, T, width, heads, causal, 0);
     else if (T > 256 && T <= 288 && !causal) {
-        if (T == 257) attention_kernel<9, true><<<items, 256, 0, st>>>(qkv, out, T, width, heads, causal, attn_xmode());
-        else attention_kernel<9><<<items, 256, 0, st>>>(qkv, out, T, width, heads, causal, attn_xmode());
+        if (T == 257) attention_kernel<9, true><<<items, 256, 0, st>>>(qkv, out, T, width, heads, causal, 0);
+        else attention_kernel<9><<<items, 256, 0, st>>>(qkv, out, T, width, heads, causal, 0);
     }
     else if (T <= 32) {
         static const int attn_short = getenv("SCD_ATTN_SHORT") ? atoi(getenv("SCD_ATTN_SHORT")) : 1;      // 0: a block per item (attention_kernel<1>; A/B, same bits)
         if (attn_short) attention_short_kernel<<<(items + 3) / 4, 256, 0, st>>>(qkv, out, T, width, heads, causal, items);
-        else attention_kernel<1><<<items, 256, 0, st>>>(qkv, out, T, width, heads, causal, attn_xmode());
+        else attention_kernel<1><<<items, 256, 0, st>>>(qkv, out, T, width, heads, causal, 0);
     }
-    else if (T <= 64) attention_kernel<2><<<items, 256, 0, st>>>(qkv, out, T, width, heads, causal, attn_xmode());
-    else if (T <= 96) attention_kernel<3><<<items, 256, 0, st>>>(qkv, out, T, width, heads, causal, attn_xmode());
+    else if (T <= 64) attention_kernel<2><<<items, 256, 0, st>>>(qkv, out, T, width, heads, causal, 0);
+    else if (T <= 96) attention_kernel<3><<<items, 256, 0, st>>>(qkv, out, T, width, heads, causal, 0);
     else SCD_REQUIRE(false, "attention: no kernel for %s T = %d (served: T <= 96, T = 197, non-causal 192 < T <= 224 with SCD_ATTN_PERSIST on, "
                             "non-causal 256 < T <= 288)",
                      causal ? "causal" : "non-causal", T);

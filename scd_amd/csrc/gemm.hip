@@ -193,7 +193,7 @@ template <int BM, int ACT, bool HAS_BIAS, bool HAS_RES>
 __global__ void __launch_bounds__(BM * 2, 2) gemm_dma_kernel(const half_t* __restrict__ A, const half_t* __restrict__ W,
                                                           const float* __restrict__ bias, const half_t* __restrict__ R,
                                                           half_t* __restrict__ C, int M, int N, int K, int tiles_n, int total_tiles,
-                                                          int xmode, int ng) {
+                                                          int xmode, int ng) {   // xmode: always 0; without it <128, NONE, bias> needs 3 more VGPRs
     constexpr int NW = BM / 32;                       // waves: 8 or 4
     constexpr int NSLOT = BM == 256 ? 4 : 3;
     constexpr int SLOT = BM * 64 + 16384;             // A sub-tile [BM][32] + W sub-tile [256][32], fp16
@@ -454,9 +454,6 @@ __global__ void __launch_bounds__(BM * 2, 2) gemm_dma_kernel(const half_t* __res
 typedef float f32x4v __attribute__((ext_vector_type(4)));
 typedef float float2v __attribute__((ext_vector_type(2)));
 typedef _Float16 half2v __attribute__((ext_vector_type(2)));
-#ifdef SCD_ABLATE   // A/B kernel (SCD_GEMM_MFMA=16): not in the default build
-#include "ablate/gemm_dma16_kernel.h"
-#endif
 
 // ------------------------------------------------------------------------------------------------
 // Four-wave kernel: 256x256 block tile, one wave per SIMD, each wave a 128(m) x 128(n) sub-tile whose 256 accumulator
@@ -480,8 +477,6 @@ typedef _Float16 half2v __attribute__((ext_vector_type(2)));
 // the accumulators between AGPRs and VGPRs around every group), C = 0 on a tile's first sub-step instead of zeroing,
 // ds_read_b128 with counted lgkmcnt (for asm operands hipcc only emits lgkmcnt(0)); s_nop covers the MFMA -> v_accvgpr_read
 // hazard the compiler cannot see.
-#include "ablate/w4_knobs.h"      // the schedule constants of this kernel (shipped values) and the experiment hooks of rounds 3-5
-#include "ablate/w4_probes.h"     // cycle-counter probes: real code with -DSCD_ABLATE, empty otherwise
 
 // LN = 1: a LayerNorm over A's rows is folded into this GEMM.  W already carries gamma (W' = W * gamma[k]), bias carries
 //         beta (b' = b + W beta), colsum[n] = sum_k W'[n][k], and ln_rs[m] = {rstd, -mean * rstd} of the raw input rows, which
@@ -503,23 +498,18 @@ gemm_w4_kernel(const half_t* __restrict__ A, const half_t* __restrict__ W, const
                int xmode_in, int ng, const float2* __restrict__ ln_rs, const float* __restrict__ ln_colsum,
                long long* __restrict__ ln_out, int stagger_in, int img_w = 0, int img_gp = 0, int img_rows = 0) {
     static_assert(NT == 8, "wave tile is 128 x 128");
-#ifdef SCD_ABLATE
-    const int xmode = xmode_in, stagger = stagger_in;
-#else
-    // the shipped build keeps the one switch it uses (512: non-temporal C stores): the timing ablations, the cycle counters and the
-    // start-up stagger exist in the -DSCD_ABLATE build only.  With them a runtime possibility, their state (seven 64-bit counters, the
-    // probe registers) stayed live through the kernel and the residual variant spilled 11 VGPRs / 66 SGPRs (round 4)
-    // Non-temporal C stores: for the residual variants (proj, fc2) a template parameter (NTS) - as a runtime test in front of each of
-    // the tile's 32 store instructions they cost 61 branches with their exec-mask bookkeeping per tile, and with the test gone the
-    // variant needs 196 VGPRs and spills nothing; the LayerNorm-folded variants (QKV, fc1) keep the runtime test: without it the
-    // register allocator ends at 256 VGPRs with spills reloaded once per tile (hipcc 7.2, -Rpass-analysis=kernel-resource-usage)
-    const int xmode = NTS ? 512 : 0, stagger = 0; (void)xmode_in;
+    // Non-temporal C stores (a large C streams past L2, see the epilogue) are the template parameter NTS, chosen by the launcher: as a
+    // runtime test in front of each of the tile's 32 store instructions they cost the residual variants (proj, fc2) 61 branches with
+    // their exec-mask bookkeeping per tile (round 4)
+    // xmode_in, stagger_in: always 0 and unused.  Kept: without xmode_in every variant's code grows by 8-12 bytes (the kernarg layout
+    // shifts), and the build without stagger_in and without attention_persist_kernel's xmode measured 1 % slower (docs/design/gemm.md)
+    (void)xmode_in;
     (void)stagger_in;
-#endif
-    constexpr bool DMA_SPLIT = W4_DMA_SPLIT;
-    constexpr bool DEFER_ST = HAS_RES && W4_DEFER_STORES;   // residual variants: all stores after the last residual load
-    constexpr bool LATE_BAR = W4_LATE_BAR;     // the chunk's barrier after the odd sub-step's first L0 MFMAs instead of before them
-    constexpr int L0 = W4_LATE_TM * 8, LS = (64 - L0) / 8;   // first hooked MFMA; MFMAs per ring fill   // true: A part of a refill in the odd sub-step, W part in the next even one
+    constexpr bool DEFER_ST = HAS_RES;         // residual variants: all of a tile's stores after its last residual load
+    constexpr int LATE_TM = 2;                 // m-tiles of the odd sub-step that run before the chunk's barrier (they need nothing new)
+    constexpr int L0 = LATE_TM * 8;            // first MFMA of the odd sub-step behind the barrier: reads and refills hang from here on
+    constexpr int LS = (64 - L0) / 8;          // MFMAs per A ring fill in the odd sub-step (eight fills under MFMAs L0..63)
+    constexpr int RD = LN == 2 ? 2 : 3;        // residual rows in flight (m-tiles); the statistics epilogue needs the registers
     constexpr int BM = 256, BN = 256, SLOT = 65536, WPART = 32768, EPI = 2 * SLOT;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x;
@@ -551,12 +541,6 @@ gemm_w4_kernel(const half_t* __restrict__ A, const half_t* __restrict__ W, const
     const int chunks = my_tiles * nkc;
     if (chunks <= 0) return;
     const int tstride = per_xcd;
-    if (stagger > 0) {   // phase-shift the blocks of an XCD (see launch_w4): wall_clock64 ticks at 100 MHz
-        // stagger >= 2^20: whole XCDs are shifted against each other (their 32 blocks stay in lock-step and keep sharing panels in
-        // the XCD's L2) instead of the blocks inside an XCD
-        const long long target = wall_clock64() + (stagger >= (1 << 20) ? (long long)xcd * (stagger - (1 << 20)) : (long long)(slot_id & 7) * stagger);
-        while (wall_clock64() < target) __builtin_amdgcn_s_sleep(32);
-    }
     auto it_step = [&](TileIt& it) {       // t += tstride
         it.t += tstride;
         it.bnl += it.r;
@@ -595,8 +579,7 @@ gemm_w4_kernel(const half_t* __restrict__ A, const half_t* __restrict__ W, const
         }
     };
     auto chunk_ptrs = [&](const TileIt& it, int kc) {
-        int bm = it.bm, bn = it.n0 + it.bnl;
-        if (xmode & 4) { bm = 0; bn = 0; }
+        const int bm = it.bm, bn = it.n0 + it.bnl;
         ga = IMG ? A + img_chunk(kc) : A + (size_t)bm * BM * K + kc * 64;
         gw = W + (size_t)bn * BN * K + kc * 64;
         // the per-lane offsets change where the scalar pointer does - with the first chunk of a tile, never earlier: the A fills of the
@@ -611,28 +594,22 @@ gemm_w4_kernel(const half_t* __restrict__ A, const half_t* __restrict__ W, const
     // M0 = the slot's LDS base (one SGPR per slot, formed once) + an immediate: one SALU instruction per fill.  (As "s"(base + slot
     // offset + 1024 p) hipcc rebuilt the address with xor / add / mov + its own s_nop in front of every fill: five scalar
     // instructions in the lone wave's stream per fill, sixteen fills per chunk.)
-#define W4_DMA(BASE, P, SLOTLDS, PART, MOD)                                                                      \
-    asm volatile("s_add_u32 m0, %0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" MOD                        \
+#define W4_DMA(BASE, P, SLOTLDS, PART)                                                                           \
+    asm volatile("s_add_u32 m0, %0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2"                            \
                  ::"s"(SLOTLDS), "v"(((P) & 1) ? voff1 : voff0), "s"((BASE) + ((P) >> 1) * k16), "n"((PART) + (P) * 1024) : "memory", "scc")
-#if W4_RES_NT
-#define W4_RLOAD(P) __builtin_nontemporal_load((const half8*)(P))
-#else
-#define W4_RLOAD(P) (*(const half8*)(P))
-#endif
     auto issue_a = [&](int p, int slot) {
         if constexpr (IMG) {
             asm volatile("s_add_u32 m0, %0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2"
                          ::"s"(dma_lds + slot * SLOT), "v"(vimg[p]), "s"(ga), "n"(p * 1024) : "memory", "scc");
-        } else if constexpr (W4_A_NT_LN1 && LN == 1) { W4_DMA(ga, p, dma_lds + slot * SLOT, 0, " nt"); }
-        else { W4_DMA(ga, p, dma_lds + slot * SLOT, 0, W4_A_MOD); }
+        } else { W4_DMA(ga, p, dma_lds + slot * SLOT, 0); }
     };
-    auto issue_w = [&](int p, int slot) { W4_DMA(gw, p, dma_lds + slot * SLOT, WPART, W4_W_MOD); };
+    auto issue_w = [&](int p, int slot) { W4_DMA(gw, p, dma_lds + slot * SLOT, WPART); };
     auto issue = [&](const TileIt& it, int kc, int slot) {
         chunk_ptrs(it, kc);
 #pragma unroll
         for (int p = 0; p < 8; ++p) issue_a(p, slot);
 #pragma unroll
-        for (int p = 0; p < W4_TNW; ++p) issue_w(p, slot);
+        for (int p = 0; p < 8; ++p) issue_w(p, slot);
     };
     // fragment addresses: tile t adds t * 2048; k-half j uses chunk (q16 + 4j) ^ sw
     const int fsw = (c16 >> 1) & 7;
@@ -652,8 +629,7 @@ gemm_w4_kernel(const half_t* __restrict__ A, const half_t* __restrict__ W, const
     // (the closed form per chunk - two 64-bit multiply-adds - sat in the lone wave's instruction stream between two MFMA groups)
     const half_t *ga_t = A, *gw_t = W;
     auto tile_ptrs = [&]() {
-        int bm = nit.bm, bn = nit.n0 + nit.bnl;
-        if (xmode & 4) { bm = 0; bn = 0; }
+        const int bm = nit.bm, bn = nit.n0 + nit.bnl;
         ga_t = IMG ? A : A + (size_t)bm * BM * K;
         gw_t = W + (size_t)bn * BN * K;
     };
@@ -669,15 +645,7 @@ gemm_w4_kernel(const half_t* __restrict__ A, const half_t* __restrict__ W, const
     if (chunks > 1) chunk_ptrs(nit, nkt); else chunk_ptrs(cit, 0);
 #pragma unroll
     for (int p = 0; p < 8; ++p) issue_a(p, 1);
-    if (!DMA_SPLIT) {
-#pragma unroll
-        for (int p = 0; p < W4_TNW; ++p) issue_w(p, 1);
-    } else if (W4_WSPLIT) {
-#pragma unroll
-        for (int p = 0; p < W4_WSPLIT; ++p) issue_w(p, 1);     // (what an odd sub-step would have issued of chunk 1's W part)
-    }
     issue_advance();
-    constexpr int RD = LN == 2 ? W4_RD_LN2 : 3;   // residual rows in flight (m-tiles); the stats epilogue needs the registers
     half8 rq[RD][4];
 #pragma unroll
     for (int e = 0; e < RD; ++e)
@@ -686,25 +654,10 @@ gemm_w4_kernel(const half_t* __restrict__ A, const half_t* __restrict__ W, const
 #pragma unroll
             for (int q = 0; q < 8; ++q) rq[e][p][q] = (half_t)0.f;
 
-    // timing probe (build with -DW4_PROBE_VALU=n): n independent VALU instructions behind every MFMA - what an epilogue dealt over
-    // the next tile's MFMA stream would add to the wave's instruction stream
-    float pv0 = 1.f + lane, pv1 = 2.f + lane, pv2 = 3.f + lane, pv3 = 0.5f;
-#if W4_PROBE_VALU == 0
-#define W4_PROBE()
-#elif W4_PROBE_VALU == 1
-#define W4_PROBE() asm volatile("v_fma_f32 %0, %0, %0, %0" : "+v"(pv0));
-#elif W4_PROBE_VALU == 2
-#define W4_PROBE() asm volatile("v_fma_f32 %0, %0, %0, %0\n\tv_fma_f32 %1, %1, %1, %1" : "+v"(pv0), "+v"(pv1));
-#elif W4_PROBE_VALU == 3
-#define W4_PROBE() asm volatile("v_fma_f32 %0, %0, %0, %0\n\tv_fma_f32 %1, %1, %1, %1\n\tv_fma_f32 %2, %2, %2, %2" : "+v"(pv0), "+v"(pv1), "+v"(pv2));
-#else
-#define W4_PROBE() asm volatile("v_fma_f32 %0, %0, %0, %0\n\tv_exp_f32 %1, %1\n\tv_fma_f32 %2, %2, %2, %2" : "+v"(pv0), "+v"(pv3), "+v"(pv2));
-#endif
     half8 fwA[8], fwB[8], faA[8], faB[8];   // W / A fragments of the even (A) and odd (B) sub-step
 #define W4_RD(DST, ADDR, OFF) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(DST) : "v"(ADDR), "n"(OFF))
 #define W4_LGKM(N) asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(N))
-    if (DMA_SPLIT) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(8 + W4_WSPLIT) : "memory");
-    else asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
+    asm volatile("s_waitcnt vmcnt(8)" ::: "memory");   // chunk 0 has landed; chunk 1's A part (eight fills) may still fly
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
 #pragma unroll
@@ -717,73 +670,47 @@ gemm_w4_kernel(const half_t* __restrict__ A, const half_t* __restrict__ W, const
     // has to issue - the fragment reads of the NEXT sub-step and the ring refill - is spread between the MFMAs through the
     // hook: issued back to back they hold up the wave's in-order instruction stream, and with it the matrix pipe, for as
     // long as the LDS / texture queues take to accept them.
-#define W4_SUB(FW, FA, Z, HOOK) W4_SUB_RANGE(FW, FA, Z, HOOK, 0, 8)
 #define W4_SUB_RANGE(FW, FA, Z, HOOK, TM0, TM1)                                                                  \
     __builtin_amdgcn_s_setprio(1);                                                                               \
-    _Pragma("unroll") for (int o_ = (TM0); o_ < (TM1); ++o_) _Pragma("unroll") for (int i_ = 0; i_ < W4_TNW; ++i_) {     \
-        const int tm = W4_TN_MAJOR ? i_ : o_, tn = W4_TN_MAJOR ? o_ : i_;                                        \
+    _Pragma("unroll") for (int tm = (TM0); tm < (TM1); ++tm) _Pragma("unroll") for (int tn = 0; tn < 8; ++tn) {  \
         if (Z) asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, 0" : "=a"(acc[tn][tm]) : "v"(FW[tn]), "v"(FA[tm]));         \
         else asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, %0" : "+a"(acc[tn][tm]) : "v"(FW[tn]), "v"(FA[tm]));          \
-        HOOK(o_ * W4_TNW + i_)                                                                                   \
-        W4_PROBE()                                                                                               \
+        HOOK(tm * 8 + tn)                                                                                        \
     }                                                                                                            \
     __builtin_amdgcn_s_setprio(0);
 #define W4_H_NONE(i)
     // even sub-step: reads the odd sub-step's fragments (k-half 1 of the same slot) under MFMAs 0..47 and issues the W part
     // of the refill that the previous odd sub-step began (the other slot), one fill per four MFMAs of the first half
-#if W4_TNW == 8
 #define W4_H_EVEN(i)                                                                                             \
-    if (DMA_SPLIT && !W4_WSPLIT && (i) < 32 && ((i) & 3) == 2) issue_w(((i) >> 2) & 7, cslot ^ 1);               \
-    if (DMA_SPLIT && W4_WSPLIT && (i) < 4 * (8 - W4_WSPLIT) && ((i) & 3) == 2) issue_w((W4_WSPLIT + ((i) >> 2)) & 7, cslot ^ 1); \
+    if ((i) < 32 && ((i) & 3) == 2) issue_w(((i) >> 2) & 7, cslot ^ 1);                                          \
     if ((i) < 48 && (i) % 3 == 0) W4_RD(fwB[((i) / 3) & 7], fw1 + so, (((i) / 3) & 7) * 2048);                   \
     if ((i) < 48 && (i) % 3 == 1) W4_RD(faB[((i) / 3) & 7], fa1 + so, (((i) / 3) & 7) * 2048);
-    // odd sub-step: reads the next chunk's first fragments (other slot) under MFMAs 0..47 and starts refilling this slot with
-    // chunk c+2: the A part (the one that can miss L2), one fill per eight MFMAs.  Measured: a wave is held ~64 cycles per
-    // fill while the CU's texture path (64 B/clk) takes the four waves' 1 KB instructions, so 16 fills inside one sub-step
-    // doubled its length; spread over two sub-steps they fit under the MFMAs.
+    // odd sub-step: the chunk's barrier sits after MFMA L0-1, so everything that needs it hangs under MFMAs L0..63: the next
+    // chunk's first fragments (other slot; W under L0, L0+2, .., A under L0+16, ..) and the A part - the one that can miss L2 - of
+    // the refill of this slot with chunk c+2, one fill per LS MFMAs.  Measured: a wave is held ~64 cycles per fill while the CU's
+    // texture path (64 B/clk) takes the four waves' 1 KB instructions, so 16 fills inside one sub-step doubled its length; spread
+    // over two sub-steps they fit under the MFMAs.
 #define W4_H_ODD(i)                                                                                              \
-    if (!LATE_BAR && (i) < 48 && (i) % 3 == 0) W4_RD(fwA[((i) / 3) & 7], fw0 + no, (((i) / 3) & 7) * 2048);      \
-    if (!LATE_BAR && (i) < 48 && (i) % 3 == 1) W4_RD(faA[((i) / 3) & 7], fa0 + no, (((i) / 3) & 7) * 2048);      \
-    if (!LATE_BAR && DMA_SPLIT && ((i) & 7) == 4) issue_a(((i) >> 3) & 7, cslot);                                \
-    if (!DMA_SPLIT && ((i) & 3) == 2) { if ((i) < 32) issue_a(((i) >> 2) & 7, cslot); else issue_w(((i) >> 2) & 7, cslot); } \
-    /* LATE_BAR: the barrier sits after MFMA L0-1, so everything that needs it is packed under MFMAs L0..63 */    \
-    if (LATE_BAR && (i) >= L0 && (((i) - L0) & 1) == 0 && (((i) - L0) >> 1) < 8) W4_RD(fwA[(((i) - L0) >> 1) & 7], fw0 + no, ((((i) - L0) >> 1) & 7) * 2048); \
-    if (LATE_BAR && (i) >= L0 && (((i) - L0) & 1) == 0 && (((i) - L0) >> 1) >= 8 && (((i) - L0) >> 1) < 16) W4_RD(faA[(((i) - L0) >> 1) & 7], fa0 + no, ((((i) - L0) >> 1) & 7) * 2048); \
-    if (LATE_BAR && DMA_SPLIT && !W4_WSPLIT && (i) >= L0 && ((i) - L0) % LS == LS / 2 && ((i) - L0) / LS < 8) issue_a((((i) - L0) / LS) & 7, cslot); \
-    if (LATE_BAR && DMA_SPLIT && W4_WSPLIT && (i) >= L0 && (((i) - L0) & 3) == 1 && ((i) - L0) / 4 < 8) issue_a((((i) - L0) / 4) & 7, cslot); \
-    if (LATE_BAR && DMA_SPLIT && W4_WSPLIT && (i) >= L0 + 32 && (((i) - L0) & 3) == 1 && ((i) - L0 - 32) / 4 < W4_WSPLIT) issue_w((((i) - L0 - 32) / 4) & 7, cslot);
-#else
-    // 32 MFMAs per sub-step: 12 fragment reads under the first 24, the W part of the refill (4 instructions per wave) every 8th
-#define W4_H_EVEN(i)                                                                                             \
-    if (DMA_SPLIT && ((i) & 7) == 2) issue_w(((i) >> 3) & 3, cslot ^ 1);                                         \
-    if ((i) < 24 && ((i) & 1) == 0 && ((i) >> 1) < 4) W4_RD(fwB[((i) >> 1) & 3], fw1 + so, (((i) >> 1) & 3) * 2048); \
-    if ((i) < 24 && ((i) & 1) == 0 && ((i) >> 1) >= 4) W4_RD(faB[(((i) >> 1) - 4) & 7], fa1 + so, ((((i) >> 1) - 4) & 7) * 2048);
-#define W4_H_ODD(i)                                                                                              \
-    if ((i) >= 8 && (((i) - 8) & 1) == 0 && (((i) - 8) >> 1) < 4) W4_RD(fwA[(((i) - 8) >> 1) & 3], fw0 + no, ((((i) - 8) >> 1) & 3) * 2048); \
-    if ((i) >= 8 && (((i) - 8) & 1) == 0 && (((i) - 8) >> 1) >= 4) W4_RD(faA[((((i) - 8) >> 1) - 4) & 7], fa0 + no, (((((i) - 8) >> 1) - 4) & 7) * 2048); \
-    if (DMA_SPLIT && (i) >= 8 && ((i) - 8) % 3 == 1 && ((i) - 8) / 3 < 8) issue_a((((i) - 8) / 3) & 7, cslot);
-#endif
+    if ((i) >= L0 && (((i) - L0) & 1) == 0 && (((i) - L0) >> 1) < 8) W4_RD(fwA[(((i) - L0) >> 1) & 7], fw0 + no, ((((i) - L0) >> 1) & 7) * 2048); \
+    if ((i) >= L0 && (((i) - L0) & 1) == 0 && (((i) - L0) >> 1) >= 8 && (((i) - L0) >> 1) < 16) W4_RD(faA[(((i) - L0) >> 1) & 7], fa0 + no, ((((i) - L0) >> 1) & 7) * 2048); \
+    if ((i) >= L0 && ((i) - L0) % LS == LS / 2 && ((i) - L0) / LS < 8) issue_a((((i) - L0) / LS) & 7, cslot);
 #define W4_EVEN(Z)                                                                                               \
     {                                                                                                            \
         const unsigned so = cslot * SLOT;                                                                        \
         W4_LGKM(0);                                                                                              \
-        W4_PROBE_SUB(t_odd)                                                                                      \
-        W4_SUB(fwA, faA, Z, W4_H_EVEN)                                                                           \
+        W4_SUB_RANGE(fwA, faA, Z, W4_H_EVEN, 0, 8)                                                               \
     }
 #define W4_ODD()                                                                                                 \
     {                                                                                                            \
         const unsigned no = (cslot ^ 1) * SLOT; /* past the last chunk: a stale slot, values unused */           \
         /* all of this wave's reads of the chunk have completed: after the barrier the slot can be refilled */   \
         W4_LGKM(0);                                                                                              \
-        W4_PROBE_SUB(t_even)                                                                                     \
         /* chunk g+1: A part issued under the previous odd sub-step, W part under the even one just finished; an epilogue's  \
            stores, if any, sit between the two in the in-order queue, so this waits for them as well */                 \
-        if (LATE_BAR) { W4_SUB_RANGE(fwB, faB, 0, W4_H_NONE, 0, W4_LATE_TM) }   /* MFMAs that need nothing new */    \
-        if (!(xmode & 8)) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                                       \
+        W4_SUB_RANGE(fwB, faB, 0, W4_H_NONE, 0, LATE_TM)   /* MFMAs that need nothing new */                     \
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                                                         \
         __builtin_amdgcn_s_barrier();                                                                            \
         asm volatile("" ::: "memory");                                                                           \
-        W4_PROBE_BAR()                                                                                           \
-        tile_first = false;                                                                                      \
         /* past this block's last chunk the refill re-reads the current tile's first chunk into the free slot: no branch  \
            around the asm groups (a diamond makes hipcc copy accumulators between paths), and nothing reads the slot */   \
         if (g + 2 < chunks) {                                                                                    \
@@ -792,23 +719,19 @@ gemm_w4_kernel(const half_t* __restrict__ A, const half_t* __restrict__ W, const
             if constexpr (IMG) { if (nkt == 0) img_offsets(nit.bm); }                                            \
         } else chunk_ptrs(cit, 0);                                                                               \
         issue_advance();                                                                                         \
-        if (LATE_BAR) { W4_SUB_RANGE(fwB, faB, 0, W4_H_ODD, W4_LATE_TM, 8) } else { W4_SUB(fwB, faB, 0, W4_H_ODD) }  \
+        W4_SUB_RANGE(fwB, faB, 0, W4_H_ODD, LATE_TM, 8)                                                          \
         cslot ^= 1;                                                                                              \
         ++g;                                                                                                     \
     }
-    W4_PROBE_DECL()
-    bool tile_first = true;      // (-DSCD_ABLATE, SCD_GEMM_X & 2048: the wait + barrier counter takes a tile's FIRST chunk only - the one behind the previous tile's stores)
     for (int ti = 0; ti < my_tiles; ++ti) {
-        tile_first = true;
         const int bm = cit.bm, bn = cit.n0 + cit.bnl;
         const int nb0 = bn * BN + wn * 128;
         // C / R addresses of the epilogue = a wave-uniform tile base (SGPRs) + ONE 32-bit per-lane element offset (row q16 of the
         // wave's rows, column piece c16): as 64-bit per-lane pointers the loop-invariant parts were hoisted into VGPR pairs that
         // lived through the kernel, and the residual variant spilled ten of them (round 4)
-        const size_t tile_el = ((size_t)((xmode & 1024) ? 0 : bm) * BM + wm * 128) * N + ((xmode & 1024) ? wn * 128 : nb0);
+        const size_t tile_el = ((size_t)bm * BM + wm * 128) * N + nb0;
         const half_t* const Rt = HAS_RES ? R + tile_el : nullptr;
         half_t* const Ct = C + tile_el;
-        W4_PROBE_MARK(t0)
         f32x4v acc[8][8];   // [tn][tm]; first written by the C = 0 MFMAs of the first sub-step
         f32x4v bq[8], sq[8];
         float2 lrs[8];
@@ -819,26 +742,21 @@ gemm_w4_kernel(const half_t* __restrict__ A, const half_t* __restrict__ W, const
     {                                                                                                            \
         if (HAS_RES) {                                                                                           \
             _Pragma("unroll") for (int e = 0; e < RD - 1; ++e) _Pragma("unroll") for (int p = 0; p < 4; ++p) rq[e][p] = \
-                W4_RLOAD(Rt + (size_t)((e * 16 + p * 4) * N) + lane_el);                                       \
+                *(const half8*)(Rt + (size_t)((e * 16 + p * 4) * N) + lane_el);                                \
         }                                                                                                        \
-        if (HAS_BIAS && W4_ABL_PRE) {                                                                            \
-            _Pragma("unroll") for (int tn = 0; tn < 8; ++tn) { bq[tn][0] = 0.f; bq[tn][1] = 0.f; bq[tn][2] = 0.f; bq[tn][3] = 0.f; sq[tn] = bq[tn]; } \
-        }                                                                                                        \
-        if (HAS_BIAS && !W4_ABL_PRE) {                                                                           \
+        if (HAS_BIAS) {                                                                                          \
             _Pragma("unroll") for (int tn = 0; tn < 8; ++tn) {                                                   \
                 const float4 b4 = *(const float4*)(bias + nb0 + tn * 16 + q16 * 4);                              \
                 bq[tn][0] = b4.x; bq[tn][1] = b4.y; bq[tn][2] = b4.z; bq[tn][3] = b4.w;                          \
             }                                                                                                    \
         }                                                                                                        \
-        if (LN == 1 && W4_LN_ABL < 2 && !W4_ABL_PRE) {                                                                          \
+        if (LN == 1) {                                                                                           \
             _Pragma("unroll") for (int tn = 0; tn < 8; ++tn) {                                                   \
                 const float4 c4 = *(const float4*)(ln_colsum + nb0 + tn * 16 + q16 * 4);                         \
                 sq[tn][0] = c4.x; sq[tn][1] = c4.y; sq[tn][2] = c4.z; sq[tn][3] = c4.w;                          \
             }                                                                                                    \
-            if (W4_LN_ABL == 0) {                                                                                \
-                _Pragma("unroll") for (int tm = 0; tm < 8; ++tm)                                                 \
-                    lrs[tm] = ln_rs[(size_t)bm * BM + wm * 128 + tm * 16 + c16];                                 \
-            }                                                                                                    \
+            _Pragma("unroll") for (int tm = 0; tm < 8; ++tm)                                                     \
+                lrs[tm] = ln_rs[(size_t)bm * BM + wm * 128 + tm * 16 + c16];                                     \
         }                                                                                                        \
     }
         if (nkc == 1) W4_PRE()
@@ -852,157 +770,146 @@ gemm_w4_kernel(const half_t* __restrict__ A, const half_t* __restrict__ W, const
 #undef W4_PRE
         W4_LGKM(0);                                            // next tile's first fragments (read under the last group)
         asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");   // last MFMA -> accumulator read
-        W4_PROBE_MARK(t1)
-        if (!(xmode & 16)) {
-            // epilogue, one 16-row m-tile at a time through a per-wave LDS patch [16 m][128 n] fp16 (256-B rows, chunk XOR row):
-            // lane (c16 = m, q16) holds n = tn*16 + q16*4 + 0..3; rows leave as whole 256-byte segments.  No lgkmcnt waits
-            // between the patch writes and reads: one wave's LDS operations execute in order.  Residual rows are fetched two
-            // m-tiles ahead (ring of three).
-            char* ep = smem + EPI + wave * 4096;
-            // software pipeline over the 8 m-tiles: the patch read of m-tile tm-1 is in flight while m-tile tm is converted,
-            // and its rows are stored after that (one wave per SIMD: nothing else would cover the LDS round trip)
-            half8 hvb[4];
-            unsigned stash[8][16];
-            float rstd_a[8], nmr_a[8];
-            if (LN == 1 && W4_LN_ABL) {
+        // epilogue, one 16-row m-tile at a time through a per-wave LDS patch [16 m][128 n] fp16 (256-B rows, chunk XOR row):
+        // lane (c16 = m, q16) holds n = tn*16 + q16*4 + 0..3; rows leave as whole 256-byte segments.  No lgkmcnt waits
+        // between the patch writes and reads: one wave's LDS operations execute in order.  Residual rows are fetched two
+        // m-tiles ahead (ring of three).
+        char* ep = smem + EPI + wave * 4096;
+        // software pipeline over the 8 m-tiles: the patch read of m-tile tm-1 is in flight while m-tile tm is converted,
+        // and its rows are stored after that (one wave per SIMD: nothing else would cover the LDS round trip)
+        half8 hvb[4];
+        unsigned stash[8][16];
+        float rstd_a[8], nmr_a[8];
+        if (LN == 1) {
+            // {rstd, -mean * rstd} of the row, formed once per row by ln_finish_kernel from the fixed-point row sums (as eight
+            // 64-bit loads + conversions per lane and tile, in front of every epilogue, they cost 2 % of an encode: round 5)
 #pragma unroll
-                for (int tm = 0; tm < 8; ++tm) { rstd_a[tm] = 1.f; nmr_a[tm] = 0.f; }
-            } else if (LN == 1) {
-                // {rstd, -mean * rstd} of the row, formed once per row by ln_finish_kernel from the fixed-point row sums (as eight
-                // 64-bit loads + conversions per lane and tile, in front of every epilogue, they cost 2 % of an encode: round 5)
+            for (int tm = 0; tm < 8; ++tm) { rstd_a[tm] = lrs[tm].x; nmr_a[tm] = lrs[tm].y; }
+        }
 #pragma unroll
-                for (int tm = 0; tm < 8; ++tm) { rstd_a[tm] = lrs[tm].x; nmr_a[tm] = lrs[tm].y; }
-            }
+        for (int tm = 0; tm <= 8; ++tm) {
+            if (tm < 8) {
+                float rstd = 1.f, nmr = 0.f;
+                if (LN == 1) { rstd = rstd_a[tm]; nmr = nmr_a[tm]; }
 #pragma unroll
-            for (int tm = 0; tm <= 8; ++tm) {
-                if (tm < 8) {
-                    float rstd = 1.f, nmr = 0.f;
-                    if (LN == 1) { rstd = rstd_a[tm]; nmr = nmr_a[tm]; }
-#pragma unroll
-                    for (int tn = 0; tn < 8; ++tn) {
-                        // four values as two register pairs, so that bias / LayerNorm terms are packed-fp32 operations and the
-                        // fp16 conversion is v_cvt_pk_f16_f32 (8-10 VALU instructions per 4 values instead of 14)
-                        float2v v01, v23;
-                        asm volatile("v_accvgpr_read_b32 %0, %1" : "=v"(v01.x) : "a"(acc[tn][tm][0]));
-                        asm volatile("v_accvgpr_read_b32 %0, %1" : "=v"(v01.y) : "a"(acc[tn][tm][1]));
-                        asm volatile("v_accvgpr_read_b32 %0, %1" : "=v"(v23.x) : "a"(acc[tn][tm][2]));
-                        asm volatile("v_accvgpr_read_b32 %0, %1" : "=v"(v23.y) : "a"(acc[tn][tm][3]));
-                        if (LN == 1 && W4_LN_ABL < 2) {
-                            const float2v r2 = {rstd, rstd}, m2 = {nmr, nmr};
-                            float2v t01 = m2 * sq[tn].lo, t23 = m2 * sq[tn].hi;
-                            if (HAS_BIAS) { t01 += bq[tn].lo; t23 += bq[tn].hi; }
-                            v01 = v01 * r2 + t01;
-                            v23 = v23 * r2 + t23;
-                        } else if (HAS_BIAS) {
-                            v01 += bq[tn].lo;
-                            v23 += bq[tn].hi;
-                        }
-                        if (ACT == SCD_ACT_QUICKGELU) {
-                            // x * sigmoid(1.702 x) = x * rcp(1 + 2^(-1.702 log2(e) x)): the three non-transcendental steps packed
-                            const float2v c2 = {-1.702f * 1.4426950408889634f, -1.702f * 1.4426950408889634f};
-                            const float2v one2 = {1.f, 1.f};
-                            float2v e01 = v01 * c2, e23 = v23 * c2;
-                            e01.x = __builtin_amdgcn_exp2f(e01.x); e01.y = __builtin_amdgcn_exp2f(e01.y);
-                            e23.x = __builtin_amdgcn_exp2f(e23.x); e23.y = __builtin_amdgcn_exp2f(e23.y);
-                            e01 += one2; e23 += one2;
-                            e01.x = __builtin_amdgcn_rcpf(e01.x); e01.y = __builtin_amdgcn_rcpf(e01.y);
-                            e23.x = __builtin_amdgcn_rcpf(e23.x); e23.y = __builtin_amdgcn_rcpf(e23.y);
-                            v01 *= e01; v23 *= e23;
-                        } else if (ACT == SCD_ACT_GELU) {
-                            v01 = gelu_erf_pair(v01); v23 = gelu_erf_pair(v23);
-                        }
-                        const half2v h01 = __builtin_convertvector(v01, half2v), h23 = __builtin_convertvector(v23, half2v);
-                        const half4 o = {h01.x, h01.y, h23.x, h23.y};
-                        *(half4*)(ep + c16 * 256 + (((tn * 2 + (q16 >> 1)) ^ c16) << 4) + (q16 & 1) * 8) = o;
+                for (int tn = 0; tn < 8; ++tn) {
+                    // four values as two register pairs, so that bias / LayerNorm terms are packed-fp32 operations and the
+                    // fp16 conversion is v_cvt_pk_f16_f32 (8-10 VALU instructions per 4 values instead of 14)
+                    float2v v01, v23;
+                    asm volatile("v_accvgpr_read_b32 %0, %1" : "=v"(v01.x) : "a"(acc[tn][tm][0]));
+                    asm volatile("v_accvgpr_read_b32 %0, %1" : "=v"(v01.y) : "a"(acc[tn][tm][1]));
+                    asm volatile("v_accvgpr_read_b32 %0, %1" : "=v"(v23.x) : "a"(acc[tn][tm][2]));
+                    asm volatile("v_accvgpr_read_b32 %0, %1" : "=v"(v23.y) : "a"(acc[tn][tm][3]));
+                    if (LN == 1) {
+                        const float2v r2 = {rstd, rstd}, m2 = {nmr, nmr};
+                        float2v t01 = m2 * sq[tn].lo, t23 = m2 * sq[tn].hi;
+                        if (HAS_BIAS) { t01 += bq[tn].lo; t23 += bq[tn].hi; }
+                        v01 = v01 * r2 + t01;
+                        v23 = v23 * r2 + t23;
+                    } else if (HAS_BIAS) {
+                        v01 += bq[tn].lo;
+                        v23 += bq[tn].hi;
                     }
+                    if (ACT == SCD_ACT_QUICKGELU) {
+                        // x * sigmoid(1.702 x) = x * rcp(1 + 2^(-1.702 log2(e) x)): the three non-transcendental steps packed
+                        const float2v c2 = {-1.702f * 1.4426950408889634f, -1.702f * 1.4426950408889634f};
+                        const float2v one2 = {1.f, 1.f};
+                        float2v e01 = v01 * c2, e23 = v23 * c2;
+                        e01.x = __builtin_amdgcn_exp2f(e01.x); e01.y = __builtin_amdgcn_exp2f(e01.y);
+                        e23.x = __builtin_amdgcn_exp2f(e23.x); e23.y = __builtin_amdgcn_exp2f(e23.y);
+                        e01 += one2; e23 += one2;
+                        e01.x = __builtin_amdgcn_rcpf(e01.x); e01.y = __builtin_amdgcn_rcpf(e01.y);
+                        e23.x = __builtin_amdgcn_rcpf(e23.x); e23.y = __builtin_amdgcn_rcpf(e23.y);
+                        v01 *= e01; v23 *= e23;
+                    } else if (ACT == SCD_ACT_GELU) {
+                        v01 = gelu_erf_pair(v01); v23 = gelu_erf_pair(v23);
+                    }
+                    const half2v h01 = __builtin_convertvector(v01, half2v), h23 = __builtin_convertvector(v23, half2v);
+                    const half4 o = {h01.x, h01.y, h23.x, h23.y};
+                    *(half4*)(ep + c16 * 256 + (((tn * 2 + (q16 >> 1)) ^ c16) << 4) + (q16 & 1) * 8) = o;
                 }
-                if (tm > 0) {
-                    const int ts = tm - 1;
+            }
+            if (tm > 0) {
+                const int ts = tm - 1;
 #pragma unroll
-                    for (int p = 0; p < 4; ++p) {
-                        const int rr = p * 4 + q16;
-                        half8 hv = hvb[p];
-                        half_t* const crow = Ct + (size_t)((ts * 16 + p * 4) * N);          // wave-uniform (residual variants)
-                        (void)rr;
-                        if (HAS_RES) hv = hv + rq[ts % RD][p];   // fp16 add of two fp16 values: the same rounding as via fp32
-                        if (LN == 2 && !W4_ABL_STATS) {
-                            // row sums of the stored fp16 values over this wave's 128 columns: 8 values in-lane, then the 16 lanes
-                            // (c16) that share row rr by DPP (rotations by 8 and 4 inside the 16-lane row, then inside the quad)
-                            float s1 = 0.f, s2 = 0.f;
-                            const half2v ones = {(half_t)1.f, (half_t)1.f};
+                for (int p = 0; p < 4; ++p) {
+                    half8 hv = hvb[p];
+                    half_t* const crow = Ct + (size_t)((ts * 16 + p * 4) * N);          // wave-uniform (residual variants)
+                    if (HAS_RES) hv = hv + rq[ts % RD][p];   // fp16 add of two fp16 values: the same rounding as via fp32
+                    if (LN == 2) {
+                        // row sums of the stored fp16 values over this wave's 128 columns: 8 values in-lane, then the 16 lanes
+                        // (c16) that share row rr by DPP (rotations by 8 and 4 inside the 16-lane row, then inside the quad)
+                        float s1 = 0.f, s2 = 0.f;
+                        const half2v ones = {(half_t)1.f, (half_t)1.f};
 #pragma unroll
-                            for (int q = 0; q < 4; ++q) {   // v_dot2_f32_f16: exact fp16 products, fp32 accumulation
-                                const half2v pr = {hv[2 * q], hv[2 * q + 1]};
-                                s1 = __builtin_amdgcn_fdot2(pr, ones, s1, false);
-                                s2 = __builtin_amdgcn_fdot2(pr, pr, s2, false);
-                            }
+                        for (int q = 0; q < 4; ++q) {   // v_dot2_f32_f16: exact fp16 products, fp32 accumulation
+                            const half2v pr = {hv[2 * q], hv[2 * q + 1]};
+                            s1 = __builtin_amdgcn_fdot2(pr, ones, s1, false);
+                            s2 = __builtin_amdgcn_fdot2(pr, pr, s2, false);
+                        }
 #define W4_DPP_ADD(V, CTRL) V += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, V), CTRL, 0xF, 0xF, true))
-                            W4_DPP_ADD(s1, 0x128); W4_DPP_ADD(s2, 0x128);   // row_ror:8
-                            W4_DPP_ADD(s1, 0x124); W4_DPP_ADD(s2, 0x124);   // row_ror:4
-                            W4_DPP_ADD(s1, 0x4E); W4_DPP_ADD(s2, 0x4E);     // quad_perm [2,3,0,1]
-                            W4_DPP_ADD(s1, 0xB1); W4_DPP_ADD(s2, 0xB1);     // quad_perm [1,0,3,2]
+                        W4_DPP_ADD(s1, 0x128); W4_DPP_ADD(s2, 0x128);   // row_ror:8
+                        W4_DPP_ADD(s1, 0x124); W4_DPP_ADD(s2, 0x124);   // row_ror:4
+                        W4_DPP_ADD(s1, 0x4E); W4_DPP_ADD(s2, 0x4E);     // quad_perm [2,3,0,1]
+                        W4_DPP_ADD(s1, 0xB1); W4_DPP_ADD(s2, 0xB1);     // quad_perm [1,0,3,2]
 #undef W4_DPP_ADD
-                            // every lane of the row group now holds the totals; lane c16 keeps those of (tm*4+p) == c16 (mod 16)
-                            const bool mine = ((ts * 4 + p) & 15) == c16;
-                            keep1[ts >> 2] = mine ? s1 : keep1[ts >> 2];
-                            keep2[ts >> 2] = mine ? s2 : keep2[ts >> 2];
-                        }
-                        // a large C streams past L2 ("nt"): written normally, each round of tiles pushes 32 MB of dirty lines
-                        // through the 32 MB of L2 and evicts the W panels every CU is about to re-read (measured +12 % on the
-                        // n = 2304 / 3072 shapes, nothing on n = 768)
-                        if (DEFER_ST) {
-                            // residual variants: a row's residual load issued behind earlier rows' stores waits in the in-order
-                            // queue until those have drained (measured: 17 k cycles of epilogue against 6 k without the stores).
-                            // The finished rows are parked in the accumulator registers their m-tile has just vacated and all
-                            // 32 stores are issued after the last residual load.
-                            const uint4 w4 = __builtin_bit_cast(uint4, hv);
-                            asm volatile("v_accvgpr_write_b32 %0, %1" : "=a"(stash[ts][p * 4 + 0]) : "v"(w4.x));
-                            asm volatile("v_accvgpr_write_b32 %0, %1" : "=a"(stash[ts][p * 4 + 1]) : "v"(w4.y));
-                            asm volatile("v_accvgpr_write_b32 %0, %1" : "=a"(stash[ts][p * 4 + 2]) : "v"(w4.z));
-                            asm volatile("v_accvgpr_write_b32 %0, %1" : "=a"(stash[ts][p * 4 + 3]) : "v"(w4.w));
-                        } else if (xmode & 2) { /* ablation: no stores */
-                        } else if (xmode & 512) {
-                            // (s_nop 1 behind every asm store: a VMEM store of more than 64 bits must not be followed within two wait
-                            // states by a write of its data registers, and hipcc's hazard recognizer cannot see a store inside inline asm -
-                            // the deferred-store loop below refills the same four registers for the next store right away.  Round 4: with
-                            // the per-store branches gone the big launches wrote corrupted rows until the nops went in)
-                            asm volatile("global_store_dwordx4 %0, %1, %2 nt\n\ts_nop 1" ::"v"(lane_el * 2u), "v"(hv), "s"(crow) : "memory");
-                        } else *(half8*)(crow + lane_el) = hv;
+                        // every lane of the row group now holds the totals; lane c16 keeps those of (tm*4+p) == c16 (mod 16)
+                        const bool mine = ((ts * 4 + p) & 15) == c16;
+                        keep1[ts >> 2] = mine ? s1 : keep1[ts >> 2];
+                        keep2[ts >> 2] = mine ? s2 : keep2[ts >> 2];
                     }
-                }
-                if (HAS_RES && tm < 8 && tm + RD - 1 < 8) {
-#pragma unroll
-                    for (int p = 0; p < 4; ++p)
-                        rq[(tm + RD - 1) % RD][p] = W4_RLOAD(Rt + (size_t)(((tm + RD - 1) * 16 + p * 4) * N) + lane_el);
-                }
-                if (tm < 8) {
-#pragma unroll
-                    for (int p = 0; p < 4; ++p) {
-                        const int rr = p * 4 + q16;
-                        hvb[p] = *(const half8*)(ep + rr * 256 + ((c16 ^ rr) << 4));
-                    }
+                    // a large C streams past L2 ("nt"): written normally, each round of tiles pushes 32 MB of dirty lines
+                    // through the 32 MB of L2 and evicts the W panels every CU is about to re-read (measured +12 % on the
+                    // n = 2304 / 3072 shapes, nothing on n = 768)
+                    if (DEFER_ST) {
+                        // residual variants: a row's residual load issued behind earlier rows' stores waits in the in-order
+                        // queue until those have drained (measured: 17 k cycles of epilogue against 6 k without the stores).
+                        // The finished rows are parked in the accumulator registers their m-tile has just vacated and all
+                        // 32 stores are issued after the last residual load.
+                        const uint4 w4 = __builtin_bit_cast(uint4, hv);
+                        asm volatile("v_accvgpr_write_b32 %0, %1" : "=a"(stash[ts][p * 4 + 0]) : "v"(w4.x));
+                        asm volatile("v_accvgpr_write_b32 %0, %1" : "=a"(stash[ts][p * 4 + 1]) : "v"(w4.y));
+                        asm volatile("v_accvgpr_write_b32 %0, %1" : "=a"(stash[ts][p * 4 + 2]) : "v"(w4.z));
+                        asm volatile("v_accvgpr_write_b32 %0, %1" : "=a"(stash[ts][p * 4 + 3]) : "v"(w4.w));
+                    } else if (NTS) {
+                        // (s_nop 1 behind every asm store: a VMEM store of more than 64 bits must not be followed within two wait
+                        // states by a write of its data registers, and hipcc's hazard recognizer cannot see a store inside inline asm -
+                        // the deferred-store loop below refills the same four registers for the next store right away.  Round 4: with
+                        // the per-store branches gone the big launches wrote corrupted rows until the nops went in)
+                        asm volatile("global_store_dwordx4 %0, %1, %2 nt\n\ts_nop 1" ::"v"(lane_el * 2u), "v"(hv), "s"(crow) : "memory");
+                    } else *(half8*)(crow + lane_el) = hv;
                 }
             }
-            if (DEFER_ST) {
+            if (HAS_RES && tm < 8 && tm + RD - 1 < 8) {
 #pragma unroll
-                for (int ts = 0; ts < 8; ++ts)
+                for (int p = 0; p < 4; ++p)
+                    rq[(tm + RD - 1) % RD][p] = *(const half8*)(Rt + (size_t)(((tm + RD - 1) * 16 + p * 4) * N) + lane_el);
+            }
+            if (tm < 8) {
 #pragma unroll
-                    for (int p = 0; p < 4; ++p) {
-                        uint4 w4;
-                        asm volatile("v_accvgpr_read_b32 %0, %1" : "=v"(w4.x) : "a"(stash[ts][p * 4 + 0]));
-                        asm volatile("v_accvgpr_read_b32 %0, %1" : "=v"(w4.y) : "a"(stash[ts][p * 4 + 1]));
-                        asm volatile("v_accvgpr_read_b32 %0, %1" : "=v"(w4.z) : "a"(stash[ts][p * 4 + 2]));
-                        asm volatile("v_accvgpr_read_b32 %0, %1" : "=v"(w4.w) : "a"(stash[ts][p * 4 + 3]));
-                        const half8 hv = __builtin_bit_cast(half8, w4);
-                        half_t* const crow = Ct + (size_t)((ts * 16 + p * 4) * N);
-                        if (xmode & 2) { /* ablation: no stores */
-                        } else if (xmode & 512) asm volatile("global_store_dwordx4 %0, %1, %2 nt\n\ts_nop 1" ::"v"(lane_el * 2u), "v"(hv), "s"(crow) : "memory");
-                        else *(half8*)(crow + lane_el) = hv;
-                    }
+                for (int p = 0; p < 4; ++p) {
+                    const int rr = p * 4 + q16;
+                    hvb[p] = *(const half8*)(ep + rr * 256 + ((c16 ^ rr) << 4));
+                }
             }
         }
-        if (LN == 2 && !(xmode & 16)) {
-            if (W4_ABL_STATS) { keep1[0] = keep1[1] = 0.f; keep2[0] = keep2[1] = 128.f; }   // probe: mean 0 / variance 1 rows, the atomics stay
+        if (DEFER_ST) {
+#pragma unroll
+            for (int ts = 0; ts < 8; ++ts)
+#pragma unroll
+                for (int p = 0; p < 4; ++p) {
+                    uint4 w4;
+                    asm volatile("v_accvgpr_read_b32 %0, %1" : "=v"(w4.x) : "a"(stash[ts][p * 4 + 0]));
+                    asm volatile("v_accvgpr_read_b32 %0, %1" : "=v"(w4.y) : "a"(stash[ts][p * 4 + 1]));
+                    asm volatile("v_accvgpr_read_b32 %0, %1" : "=v"(w4.z) : "a"(stash[ts][p * 4 + 2]));
+                    asm volatile("v_accvgpr_read_b32 %0, %1" : "=v"(w4.w) : "a"(stash[ts][p * 4 + 3]));
+                    const half8 hv = __builtin_bit_cast(half8, w4);
+                    half_t* const crow = Ct + (size_t)((ts * 16 + p * 4) * N);
+                    if (NTS) asm volatile("global_store_dwordx4 %0, %1, %2 nt\n\ts_nop 1" ::"v"(lane_el * 2u), "v"(hv), "s"(crow) : "memory");
+                    else *(half8*)(crow + lane_el) = hv;
+                }
+        }
+        if (LN == 2) {
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
                 // fixed point so that the six partial sums of a row (3 tile columns x 2 waves) add up deterministically
@@ -1012,15 +919,10 @@ gemm_w4_kernel(const half_t* __restrict__ A, const half_t* __restrict__ W, const
             }
         }
         if (ti + 1 < my_tiles) it_step(cit);
-        W4_PROBE_TILE_END()
     }
-    W4_PROBE_FINISH()
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the tail refills must land before the LDS is handed to another block
-    if (W4_PROBE_VALU && pv0 + pv1 + pv2 + pv3 == 12345.678f) C[0] = (half_t)pv0;
-#undef W4_PROBE
 #undef W4_EVEN
 #undef W4_ODD
-#undef W4_SUB
 #undef W4_SUB_RANGE
 #undef W4_H_NONE
 #undef W4_H_EVEN
@@ -1029,10 +931,6 @@ gemm_w4_kernel(const half_t* __restrict__ A, const half_t* __restrict__ W, const
 #undef W4_RD
 #undef W4_LGKM
 }
-
-#ifdef SCD_ABLATE   // A/B kernel (SCD_GEMM_MFMA=8): not in the default build
-#include "ablate/gemm_w8_kernel.h"
-#endif
 
 // n-tiles per group: the W panels of a group (ng*256*K*2 bytes) should stay inside one XCD's 4 MB L2; every extra group
 // re-reads the activations once.  Estimate the beyond-L2 traffic of each candidate and keep the cheapest.
@@ -1056,10 +954,6 @@ static int choose_ng(int M, int K, int tiles_n, int total, int resident) {
     return ng;
 }
 
-#ifdef SCD_ABLATE
-#include "ablate/gemm_w8_launch.h"
-#endif
-
 template <int NT, int ACT, bool B, bool RR, int LN>
 static int launch_w4(const half_t* A, const half_t* W, const float* bias, const half_t* R, half_t* C, int M, int N, int K,
                      const scd_gemm_ln* ln, hipStream_t st) {
@@ -1068,21 +962,16 @@ static int launch_w4(const half_t* A, const half_t* W, const float* bias, const 
     { const int rc_ = scd_set_max_lds((const void*)gemm_w4_kernel<NT, ACT, B, RR, LN, false>, LDS); if (rc_) return rc_; }
     { const int rc_ = scd_set_max_lds((const void*)gemm_w4_kernel<NT, ACT, B, RR, LN, true>, LDS); if (rc_) return rc_; }
     const int tiles_m = M / 256, tiles_n = N / 256, total = tiles_m * tiles_n;
-    static const int xenv = SCD_ABLATE_ENV("SCD_GEMM_X", 0);
     static const int nt_env = getenv("SCD_GEMM_NT") ? atoi(getenv("SCD_GEMM_NT")) : -1;   // -1: by size
     const bool nt = nt_env >= 0 ? nt_env != 0 : 2.0 * M * (double)N > 64e6;   // C beyond what L2 (32 MB) could keep anyway
-    const int xmode = xenv | (nt ? 512 : 0);
     const int ng = choose_ng(M, K, tiles_n, total, 256);
     const int grid = total < 256 ? (total >= 8 ? total / 8 * 8 : total) : 256;
-    static const int stagger_env = SCD_ABLATE_ENV("SCD_GEMM_STAGGER", 0);   // ticks per phase, experiment
-    const int stagger = stagger_env;
 #define W4_GO(NTSV)                                                                                                            \
-    gemm_w4_kernel<NT, ACT, B, RR, LN, NTSV><<<grid, 256, LDS, st>>>(A, W, bias, R, C, M, N, K, tiles_n, total, xmode, ng,         \
+    gemm_w4_kernel<NT, ACT, B, RR, LN, NTSV><<<grid, 256, LDS, st>>>(A, W, bias, R, C, M, N, K, tiles_n, total, 0, ng,             \
                                                                      LN == 1 ? (const float2*)ln->rs_in : nullptr, LN == 1 ? ln->colsum : nullptr, \
-                                                                     LN == 2 ? ln->stats_out : nullptr, stagger)
+                                                                     LN == 2 ? ln->stats_out : nullptr, 0)
     if (nt) W4_GO(true); else W4_GO(false);
 #undef W4_GO
-    W4_PROBE_REPORT()
     return SCD_OK;
 }
 
@@ -1100,7 +989,7 @@ int scd_gemm_launch_img(const half_t* pixels, const half_t* W, half_t* C, int64_
     const bool nt = 2.0 * M * (double)N > 64e6;
     const int ng = choose_ng((int)M, K, tiles_n, total, 256);
     const int grid = total < 256 ? (total >= 8 ? total / 8 * 8 : total) : 256;
-    if (nt) gemm_w4_kernel<8, SCD_ACT_NONE, false, false, 0, true, true><<<grid, 256, LDS, st>>>(pixels, W, nullptr, nullptr, C, (int)M, N, K, tiles_n, total, 512, ng, nullptr, nullptr, nullptr, 0, image, gp, batch * gp * gp);
+    if (nt) gemm_w4_kernel<8, SCD_ACT_NONE, false, false, 0, true, true><<<grid, 256, LDS, st>>>(pixels, W, nullptr, nullptr, C, (int)M, N, K, tiles_n, total, 0, ng, nullptr, nullptr, nullptr, 0, image, gp, batch * gp * gp);
     else gemm_w4_kernel<8, SCD_ACT_NONE, false, false, 0, false, true><<<grid, 256, LDS, st>>>(pixels, W, nullptr, nullptr, C, (int)M, N, K, tiles_n, total, 0, ng, nullptr, nullptr, nullptr, 0, image, gp, batch * gp * gp);
     SCD_LAUNCH_CHECK();
     return SCD_OK;
@@ -1109,19 +998,6 @@ int scd_gemm_launch_img(const half_t* pixels, const half_t* W, half_t* C, int64_
 // the LayerNorm-folded variants exist for the shapes the encoders use: bias, no residual (LN = 1) and bias + residual (LN = 2)
 static int launch_w4_ln(const half_t* A, const half_t* W, const float* bias, const half_t* R, half_t* C, int M, int N, int K, int act,
                         const scd_gemm_ln* ln, hipStream_t st) {
-#ifdef SCD_ABLATE
-    static const int w8 = SCD_ABLATE_ENV("SCD_GEMM_MFMA", 4) == 8;
-    if (w8) {
-        if (ln->stats_in) {
-            if (!bias || R || ln->stats_out) return SCD_EINVAL;
-            if (act == SCD_ACT_NONE) return launch_w8<SCD_ACT_NONE, true, false, 1>(A, W, bias, R, C, M, N, K, ln, st);
-            if (act == SCD_ACT_QUICKGELU) return launch_w8<SCD_ACT_QUICKGELU, true, false, 1>(A, W, bias, R, C, M, N, K, ln, st);
-            return launch_w8<SCD_ACT_GELU, true, false, 1>(A, W, bias, R, C, M, N, K, ln, st);
-        }
-        if (!bias || !R || act != SCD_ACT_NONE) return SCD_EINVAL;
-        return launch_w8<SCD_ACT_NONE, true, true, 2>(A, W, bias, R, C, M, N, K, ln, st);
-    }
-#endif
     if (ln->stats_in) {
         if (!bias || R || ln->stats_out || !ln->rs_in) return SCD_EINVAL;
         if (act == SCD_ACT_NONE) return launch_w4<8, SCD_ACT_NONE, true, false, 1>(A, W, bias, R, C, M, N, K, ln, st);
@@ -1136,36 +1012,18 @@ template <int BM, int ACT, bool B, bool RR>
 static int launch_dma(const half_t* A, const half_t* W, const float* bias, const half_t* R, half_t* C, int M, int N, int K,
                       hipStream_t st) {
     constexpr int LDS = BM == 256 ? 4 * (256 * 64 + 16384) + 8 * 4096 : 3 * (128 * 64 + 16384) + 4 * 2048;   // 160 KB / 80 KB
-#ifdef SCD_ABLATE
-    { const int rc_ = scd_set_max_lds((const void*)gemm_dma_kernel<BM, ACT, B, RR>, LDS); if (rc_) return rc_; }
-#else
     if constexpr (BM != 256) { const int rc_ = scd_set_max_lds((const void*)gemm_dma_kernel<BM, ACT, B, RR>, LDS); if (rc_) return rc_; }
-#endif
     const int tiles_n = N / 256, total = (M / BM) * tiles_n;
     const int resident = BM == 256 ? 256 : 512;
     const int grid = total < resident ? (total >= 8 ? total / 8 * 8 : total) : resident;
-    static const int xmode = SCD_ABLATE_ENV("SCD_GEMM_X", 0);
     const int ng = choose_ng(M, K, tiles_n, total, resident);
-#ifdef SCD_ABLATE
-    static const int mfma_sel = SCD_ABLATE_ENV("SCD_GEMM_MFMA", 4);   // 4: four-wave kernel (default); 8 / 16 / 32: eight-wave kernels
-    if (BM == 256 && mfma_sel == 4) return launch_w4<8, ACT, B, RR, 0>(A, W, bias, R, C, M, N, K, nullptr, st);
-    if (BM == 256 && mfma_sel == 8) return launch_w8<ACT, B, RR, 0>(A, W, bias, R, C, M, N, K, nullptr, st);
-    if (BM == 256 && mfma_sel == 16) {
-        { const int rc_ = scd_set_max_lds((const void*)gemm_dma16_kernel<ACT, B, RR>, 163840); if (rc_) return rc_; }
-        gemm_dma16_kernel<ACT, B, RR><<<grid, 512, 163840, st>>>(A, W, bias, R, C, M, N, K, tiles_n, total, xmode, ng);
-        return SCD_OK;
-    }
-    gemm_dma_kernel<BM, ACT, B, RR><<<grid, BM * 2, LDS, st>>>(A, W, bias, R, C, M, N, K, tiles_n, total, xmode, ng);
-    return SCD_OK;
-#else
-    // default build: 256-row tiles go to the four-wave kernel; the eight-wave DMA kernel serves M % 256 == 128 only
+    // 256-row tiles go to the four-wave kernel; the eight-wave DMA kernel serves M % 256 == 128 only
     if constexpr (BM == 256) {
         return launch_w4<8, ACT, B, RR, 0>(A, W, bias, R, C, M, N, K, nullptr, st);
     } else {
-        gemm_dma_kernel<BM, ACT, B, RR><<<grid, BM * 2, LDS, st>>>(A, W, bias, R, C, M, N, K, tiles_n, total, xmode, ng);
+        gemm_dma_kernel<BM, ACT, B, RR><<<grid, BM * 2, LDS, st>>>(A, W, bias, R, C, M, N, K, tiles_n, total, 0, ng);
         return SCD_OK;
     }
-#endif
 }
 template <int BM, int ACT>
 static int launch_dma_act(const half_t* A, const half_t* W, const float* bias, const half_t* R, half_t* C, int M, int N, int K,
@@ -1233,11 +1091,10 @@ int scd_gemm_launch(const half_t* A, const half_t* W, const float* bias, const h
                 "gemm: shape m=%lld n=%d k=%d must be multiples of 128/128/64", (long long)M, N, K);
     SCD_REQUIRE(C != (half_t*)A, "gemm: C must not alias A");
     SCD_REQUIRE(act == SCD_ACT_NONE || act == SCD_ACT_QUICKGELU || act == SCD_ACT_GELU, "gemm: bad activation %d", act);
-    static const int force = SCD_ABLATE_ENV("SCD_GEMM_TILE", 0);    // 64 -> legacy 128x128 kernel, 128 -> 128-row DMA kernel
-    if (N % 256 == 0 && force != 64) {
+    if (N % 256 == 0) {
         int rc = -1;
         // BM=256 (one 8-wave block per CU) measures a few % ahead of BM=128 (two 4-wave blocks per CU) on the ViT shapes
-        if (M % 256 == 0 && force != 128) rc = launch_dma_bm<256>(A, W, bias, R, C, (int)M, N, K, act, st);
+        if (M % 256 == 0) rc = launch_dma_bm<256>(A, W, bias, R, C, (int)M, N, K, act, st);
         else rc = launch_dma_bm<128>(A, W, bias, R, C, (int)M, N, K, act, st);
         if (rc) return rc;
         SCD_LAUNCH_CHECK();

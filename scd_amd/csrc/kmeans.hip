@@ -198,17 +198,12 @@ __global__ void __launch_bounds__(256) ct_transpose_kernel(const float* __restri
 }
 // many centres: the transposed copy by ct_transpose_kernel behind the per-centre blocks instead of from inside them
 static inline bool ct_separate(int kp) { return kp >= 512; }
-// Only estep_refine_full_kernel reads the transposed copy: the legacy path (Kp > 2048 or Dp > 768) and, in -DSCD_ABLATE builds, the
-// split-refine switch of the streaming path.  The single-pass and the streaming path of the default build re-evaluate rows against the
-// row-major centres (refine_full_row), so there the copy is not written at all (2 MB of scattered writes per E-step at K = 1000).
+// Only estep_refine_full_kernel reads the transposed copy: the legacy path (Kp > 2048 or Dp > 768).  The single-pass and the streaming
+// path re-evaluate rows against the row-major centres (refine_full_row), so there the copy is not written at all (2 MB of scattered
+// writes per E-step at K = 1000).
 static inline bool ct_dead(int dp, int kp) {
-#ifdef SCD_ABLATE
-    (void)dp; (void)kp;
-    return false;
-#else
     static const int use_stream = getenv("SCD_ESTEP_STREAM") ? atoi(getenv("SCD_ESTEP_STREAM")) : 1;
     return use_stream && kp <= 2048 && dp <= 768;
-#endif
 }
 // what the per-centre blocks are handed / whether the tiled transpose follows them
 static inline float* ct_inline(float* ct, int dp, int kp) { return (ct_dead(dp, kp) || ct_separate(kp)) ? nullptr : ct; }
@@ -652,6 +647,7 @@ __global__ void __launch_bounds__(256) estep_stream_kernel(const half_t* __restr
                                                            const float* __restrict__ cn_all, int kp_all,
                                                            const float* __restrict__ Xf, const float* __restrict__ Cf, int d_f,
                                                            int k_f) {
+    // dbg: always 0 (timing switches of earlier rounds); without it the register allocation of NCH >= 3 needs more VGPRs / AGPRs
     // K > 128 runs one launch per 128-centre chunk (`ch` / `cn` point at the chunk, cbase = its first centre): every pass but
     // the last leaves each row's three smallest (key, centre) pairs in tkey / tidx [3][n], every pass but the first merges
     // them in; the last pass (pass & 2) takes the decisions.  pass = 1 first | 2 last.
@@ -1539,8 +1535,8 @@ __global__ void __launch_bounds__(128) estep_refine_full_kernel(const float* __r
 }
 
 // both refine passes in one launch (streaming path): all-centres rows one 8-wave block per row, pair rows one wave per row.
-#define REFINE_GRID (unsigned)SCD_ABLATE_ENV("SCD_REFINE_GRID", 1024)
-#define REFINE_PAIR SCD_ABLATE_ENV("SCD_REFINE_PAIR", 256)
+#define REFINE_GRID 1024u   // blocks of the launch
+#define REFINE_PAIR 256     // of them, blocks that take the pair rows
 __device__ __forceinline__ void refine_both_body(const float* __restrict__ X, const float* __restrict__ C, const float* __restrict__ ct,
                                                  const EHdr* eh, const int* flag_list, const int* flag_cand, const int* full_list, int d,
                                                  int k, int kp, int32_t* labels, int32_t* refine_rows_out, int pair_blocks, int bx, int gx) {
@@ -1685,18 +1681,16 @@ extern "C" int scd_kmeans_estep(scd_handle h, const float* X, const void* prep, 
         if (grid < scd_cdiv(g32, ES_RMAX / 32)) grid = scd_cdiv(g32, ES_RMAX / 32);
         const half_t* xh = (const half_t*)(p + xh_off);
         const float* xn = (const float*)(p + xnorm_off);
-        static const int es_dbg = SCD_ABLATE_ENV("SCD_ESTEP_DBG", 0);
-        static const int split = SCD_ABLATE_ENV("SCD_ESTEP_REFINE_SPLIT", 0);   // 0: refine in the stream kernel's tail
         // refine in the stream kernel's tail only when the caller expects few flagged rows (scd_kmeans_estep_hint: Lloyd iterations
         // after the first two): with ~10 % of the rows flagged the one-block-per-CU tail takes 190 us where the refine kernel at
         // full occupancy takes 60-100; with none flagged the tail saves the launch (37 -> 31 us per call)
-        const bool tail = split == 0 && d <= 1024 && few_hint;
+        const bool tail = d <= 1024 && few_hint;
 #define ES_LAUNCH(NCH)                                                                                                       \
     case NCH: {                                                                                                              \
         { const int rc_ = scd_set_max_lds((const void*)estep_stream_kernel<NCH>, ES_LDS); if (rc_) return rc_; }                                                                                                                    \
         for (int cb = 0; cb < kp / 128; ++cb)                                                                                \
             estep_stream_kernel<NCH><<<(unsigned)grid, 256, ES_LDS, st>>>(xh, xn, chf + (size_t)cb * 128 * dp, cn + cb * 128, eh, flags, fcand, \
-                                                                          fulls, n, labels_out, es_dbg, cb * 128,           \
+                                                                          fulls, n, labels_out, 0, cb * 128,                \
                                                                           (cb == 0 ? 1 : 0) | (cb == kp / 128 - 1 ? 2 : 0), tkey, tidx, cn, kp,  \
                                                                           tail ? X : nullptr, C, d, k);                       \
     } break;
@@ -1716,15 +1710,10 @@ extern "C" int scd_kmeans_estep(scd_handle h, const float* X, const void* prep, 
         }
         if (tail) {
             if (refine_rows_out) refine_count_kernel<<<1, 1, 0, st>>>(eh, refine_rows_out);
-        } else if (split == 2) {
-            // debugging: filter labels only
-        } else if (split == 1) {
-            estep_refine_kernel<<<2048, 64, 0, st>>>(X, C, eh, flags, fcand, d, k, labels_out);
-            estep_refine_full_kernel<<<2048, 128, (size_t)d * 8 + 64, st>>>(X, ct, eh, fulls, d, k, kp, labels_out);
-            if (refine_rows_out) refine_count_kernel<<<1, 1, 0, st>>>(eh, refine_rows_out);
-        } else
-        estep_refine_both_kernel<<<REFINE_GRID, 512, (size_t)d * 32 + 64, st>>>(X, C, ct, eh, flags, fcand, fulls, d, k, kp, labels_out,
-                                                                                refine_rows_out, REFINE_PAIR);
+        } else {
+            estep_refine_both_kernel<<<REFINE_GRID, 512, (size_t)d * 32 + 64, st>>>(X, C, ct, eh, flags, fcand, fulls, d, k, kp, labels_out,
+                                                                                    refine_rows_out, REFINE_PAIR);
+        }
         SCD_LAUNCH_CHECK();
         return SCD_OK;
     }

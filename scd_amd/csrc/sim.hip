@@ -301,7 +301,9 @@ __global__ void __launch_bounds__(NW * 64, NW == 4 && NDC == 8 ? 2 : 1) sim_topk
 }
 
 // ------------------------------------------------------------------------------------------------
-// Row-block kernel (d == 512, the CLIP embedding width; default).  Same outputs as the kernels above, different schedule:
+// Row-block schedule (d == 512, the CLIP embedding width), as round 2's four-wave kernel introduced it; that kernel is gone (git
+// history keeps it), its eight-wave successors below keep the units, ring, keys and lists described here.  Same outputs as the
+// kernels above, different schedule:
 //   * one wave per SIMD (256 threads, 512 registers); wave w owns 64 images (two 32-image sets) whose 2 x 32 B fragments live
 //     in 256 AGPRs and feed the MFMAs directly;
 //   * the unit of work is a block of 32 NAMES with its whole K = 512: 32 rows x 1 KB of W^T = 32 KB, ONE 1-KB LDS-DMA
@@ -326,302 +328,9 @@ __device__ __forceinline__ double rb_max64(double a, double b) { double d; asm("
 __device__ __forceinline__ double rb_min64(double a, double b) { double d; asm("v_min_f64 %0, %1, %2" : "=v"(d) : "v"(a), "v"(b)); return d; }
 #define RB_NEG -3.0e38f                    /* masks padded names: finite, so that widening + index bits stays a number */
 
-#ifdef SCD_ABLATE   // the four-wave predecessor (SCD_SIM_RB=1): kept for A/B runs, not in the default build
-template <bool SOFTMAX, int TM, int XM = 0>          // XM: timing ablations (1 no epilogue pieces, 2 no ring fills, 4 no MFMAs; results are wrong)
-__global__ void __launch_bounds__(256) sim_topk_rb_kernel(const half_t* __restrict__ F, const half_t* __restrict__ Wt, long long n,
-                                                          long long v, float scale, float* __restrict__ cand_val,
-                                                          int* __restrict__ cand_idx, float* __restrict__ stats) {
-    constexpr int D = 512, UB = 32768;
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int tid = threadIdx.x;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
-    const int r = lane & 31, hh = lane >> 5;
-    const unsigned sbase = (unsigned)(size_t)(__attribute__((address_space(3))) char*)smem;
-
-    half8 bf[2][32];
-#pragma unroll
-    for (int q = 0; q < 2; ++q) {
-        const long long img = (long long)blockIdx.x * 256 + wave * 64 + q * 32 + r;
-        const half_t* frow = F + (img < n ? img : n - 1) * D + 8 * hh;
-#pragma unroll
-        for (int s = 0; s < 32; ++s) bf[q][s] = *(const half8*)(frow + 16 * s);
-    }
-#pragma unroll
-    for (int q = 0; q < 2; ++q)
-#pragma unroll
-        for (int s = 0; s < 32; ++s) asm volatile("" : "+a"(bf[q][s]));       // resident in AGPRs from here on
-
-    double L[2][TM];                                           // per image set: the lane's TM best (key | name index), descending
-    float thr[2] = {-INFINITY, -INFINITY};                     // float view of L[q][TM-1]
-    float m1[2], m2[2], smm[2] = {-INFINITY, -INFINITY}, smz[2] = {0.f, 0.f}, nmc[2];
-    double tk[2];
-#pragma unroll
-    for (int q = 0; q < 2; ++q)
-#pragma unroll
-        for (int j = 0; j < TM; ++j) L[q][j] = -INFINITY;
-    const float c2 = scale * 1.4426950408889634f;              // exp((a - m) * scale) = exp2((a - m) * c2)
-
-    const int nunits = (int)((v + 31) / 32);
-    // ring fill: wave w stages rows 8w .. 8w+7 of a unit, one 1-KB instruction per row; lane l fetches source chunk l ^ (row & 15)
-    unsigned foff[8];
-#pragma unroll
-    for (int p = 0; p < 8; ++p) {
-        const int row = 8 * wave + p;
-        foff[p] = (unsigned)(row * 1024 + ((lane ^ (row & 15)) << 4));
-    }
-    // per unit: fbase = W^T rows of unit u+3 (scalar), fm0 = LDS address of this wave's first row in the slot; per fill only m0 moves
-    const half_t* fbase = Wt;
-    unsigned fm0 = 0;
-    bool flast = false;
-    auto fill_unit = [&](int unit) {
-        fbase = Wt + (size_t)unit * 32 * D;
-        fm0 = sbase + (unit & 3) * UB + 8 * wave * 1024;
-        flast = unit == nunits - 1;
-    };
-    auto fill = [&](int unit, int p) {
-        unsigned off = foff[p];
-        if (flast) {                                                            // padded names re-read row v-1; masked in the epilogue
-            const int row = 8 * wave + p;
-            long long vr = (long long)unit * 32 + row;
-            vr = vr < v ? vr : v - 1;
-            off = (unsigned)((int)(vr - (long long)unit * 32) * 1024 + ((lane ^ (row & 15)) << 4));
-        }
-        asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2"
-                     ::"s"(fm0 + p * 1024), "v"(off), "s"(fbase) : "memory");
-    };
-    // A fragment of k16 step s: row r, source chunk 2s + hh -> LDS chunk (2s + hh) ^ (r & 15); with j = s & 7 the byte offset is
-    // (s >> 3) * 256 + ((32 j) ^ (16 (hh ^ (r & 15)))): eight per-lane addresses + an immediate
-    unsigned fa[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) fa[j] = sbase + (unsigned)(r * 1024 + ((32 * j) ^ (16 * (hh ^ (r & 15)))));
-
-#define RB_RD(DST, J, IMM) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(DST) : "v"(fa[J]), "n"(IMM))
-#define RB_WAIT(N, FR) asm volatile("s_waitcnt lgkmcnt(" #N ")" : "+v"(FR))
-#define RB_MFMA(ACC, A, B) asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, %2, %0" : "+v"(ACC) : "v"(A), "a"(B))
-// "=&v": the destination of a multi-pass MFMA must not overlap its A / B sources (only C may be the same registers); without the
-// early clobber hipcc reuses the registers of a fragment that dies here, and the results are garbage
-#define RB_MFMA0(ACC, A, B) asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, %2, 0" : "=&v"(ACC) : "v"(A), "a"(B))
-
-    // ---- epilogue pieces of one finished unit -------------------------------------------------------------------------------
-    auto key = [](float a, int i) { return __uint_as_float((__float_as_uint(a) & 0xfffffff0u) | (unsigned)i); };
-    auto name_of = [&](int unit, int i) { return unit * 32 + (i & 3) + 8 * (i >> 2) + 4 * hh; };
-    auto p_top2 = [&](const f32x16& a, int q, int i) {         // value i into the running (largest, second) key pair
-        const float k = key(a[i], i);
-        if (i == 0) {
-            m1[q] = k;
-            m2[q] = -INFINITY;
-        } else {
-            const float n1 = rb_max(m1[q], k);
-            m2[q] = rb_med3(m1[q], m2[q], k);
-            m1[q] = n1;
-        }
-    };
-    auto widen = [&](float k, int unit) {                      // double(key) with the name index in the low mantissa word
-        const int i = (int)(__float_as_uint(k) & 15u);
-        return __hiloint2double(__double2hiint((double)k), name_of(unit, i));
-    };
-    auto p_ins = [&](int q, int j) {                           // tk[q] sinks past list entry j
-        const double hi = rb_max64(L[q][j], tk[q]);
-        if (j + 1 < TM) tk[q] = rb_min64(L[q][j], tk[q]);
-        L[q][j] = hi;
-        if (j + 1 == TM) thr[q] = (float)L[q][TM - 1];
-    };
-    auto p_ins_all = [&](int q) {
-#pragma unroll
-        for (int j = 0; j < TM; ++j) p_ins(q, j);
-    };
-    auto p_rest = [&](const f32x16& a, int q, int unit) {      // rare: the lane's second key beats its list as well
-        if (!__any(m2[q] > thr[q])) return;
-        float bound = m1[q];
-        for (;;) {
-            float c = -INFINITY;
-#pragma unroll
-            for (int i = 0; i < 16; ++i) {
-                const float k = key(a[i], i);
-                c = (k < bound && k > c) ? k : c;
-            }
-            if (!__any(c > thr[q])) break;
-            if (c > thr[q]) {
-                tk[q] = widen(c, unit);
-                p_ins_all(q);
-            }
-            bound = c;
-        }
-    };
-    auto p_sm_begin = [&](int q) {                             // new reference maximum, old sum rescaled to it
-        const float mref = rb_max(smm[q], m1[q]);
-        smz[q] = smz[q] * __builtin_amdgcn_exp2f((smm[q] - mref) * c2);          // first unit: 0 * exp2(-inf) = 0
-        smm[q] = mref;
-        nmc[q] = -mref * c2;
-    };
-    auto p_sm_add = [&](const f32x16& a, int q, int i) { smz[q] += __builtin_amdgcn_exp2f(fmaf(a[i], c2, nmc[q])); };
-    // ---- one unit: 32 k16 steps x 2 MFMAs into acc[P][], the epilogue of the previous unit (acc[1-P][]) in their shadow -------
-    // A wave is held at its second MFMA until the matrix pipe takes it, so the vector work is dealt in HALF-steps, a few
-    // instructions behind EACH MFMA (h = 2s after the first, 2s+1 after the second):
-    //   h  4..19  one value of each image set into its (largest, second) key pair
-    //   h  20     widen both winners; softmax reference maxima
-    //   h 21..36  image set 0: one list entry per half-step (max, min), one softmax term;  h 37: its rare second-key loop
-    //   h 37..52  image set 1: the same;                                                  h 53: its rare second-key loop
-    // (the accumulators are indexed with compile-time constants only: handed to a lambda by reference, hipcc keeps them in scratch)
-    f32x16 acc[2][2];
-    half8 fr[4];                                               // 32 steps per unit: the rotation phase survives the unit boundary
-    auto body = [&](auto has_prev, auto parity, int u) {
-        constexpr int P = decltype(parity)::value;
-        constexpr bool EPI = decltype(has_prev)::value && !(XM & 1);
-        // my fills of unit u+1 have landed (those of u+2 may fly); after the barrier everybody's have, and slot (u-1)&3 is free
-        if constexpr (!(XM & 512)) {
-            if (u + 2 < nunits) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-            else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        }
-        if constexpr (!(XM & 256)) __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-        const bool more = u + 1 < nunits;
-        const bool fills = u + 3 < nunits;
-        if (fills) fill_unit(u + 3);
-        static_for<0, 32>([&](auto sc) {
-            constexpr int s = decltype(sc)::value;
-            // fragment reads run THREE steps ahead and the wait of step s retires the fragment of step s+1: an MFMA issued within
-            // a few wait states of the s_waitcnt that retires its A operand's ds_read still saw the OLD register content
-            // (measured: with two-ahead reads the first MFMA of every step was wrong, the second, 32 cycles later, right).
-            // Steps 29..31 read the first three fragments of unit u+1, whose slot was published by this unit's barrier.
-            if (s == 29) {
-                const unsigned delta = ((u + 1) & 3) ? (unsigned)UB : (unsigned)(-3 * UB);      // wave-uniform
-#pragma unroll
-                for (int j = 0; j < 8; ++j) fa[j] += delta;
-            }
-            if constexpr (s < 29) RB_RD(fr[(s + 3) & 3], (s + 3) & 7, ((s + 3) >> 3) * 256);
-            else if (more) RB_RD(fr[(s + 3) & 3], (s + 3 - 32) & 7, 0);
-            if constexpr (XM & 128) { asm volatile("" : "+v"(fr[(s + 1) & 3])); }
-            else if (s < 29 || more) RB_WAIT(2, fr[(s + 1) & 3]);
-            else if (s == 29) RB_WAIT(1, fr[(s + 1) & 3]);
-            else if (s == 30) RB_WAIT(0, fr[(s + 1) & 3]);
-            static_for<0, 2>([&](auto qc) {
-                constexpr int q = decltype(qc)::value;
-                constexpr int h = 2 * s + decltype(qc)::value;
-                if constexpr (!(XM & 4)) {
-                    constexpr int PP = (XM & 8) ? ((s & 1) ? 1 - P : P) : P;        // XM & 8 (timing only): four accumulator chains
-                    if (s == 0 || ((XM & 8) && s == 1)) RB_MFMA0(acc[PP][q], fr[s & 3], bf[q][s]);
-                    else RB_MFMA(acc[PP][q], fr[s & 3], bf[q][s]);
-                }
-                if constexpr (decltype(qc)::value == 1 && !(XM & 2))
-                    if ((s & 3) == 3 && fills) fill(u + 3, s >> 2);
-                if constexpr (EPI) {
-                    if constexpr (h >= 4 && h < 20) {
-                        p_top2(acc[1 - P][0], 0, h - 4);
-                        p_top2(acc[1 - P][1], 1, h - 4);
-                    } else if constexpr (h == 20) {
-                        tk[0] = widen(m1[0], u - 1);
-                        tk[1] = widen(m1[1], u - 1);
-                        if (SOFTMAX) { p_sm_begin(0); p_sm_begin(1); }
-                    } else if constexpr (h >= 21 && h < 37) {
-                        if constexpr (h - 21 < TM) p_ins(0, h - 21);
-                        if (SOFTMAX) p_sm_add(acc[1 - P][0], 0, h - 21);
-                    }
-                    if constexpr (h >= 37 && h < 53) {
-                        if constexpr (h == 37) p_rest(acc[1 - P][0], 0, u - 1);
-                        if constexpr (h - 37 < TM) p_ins(1, h - 37);
-                        if (SOFTMAX) p_sm_add(acc[1 - P][1], 1, h - 37);
-                    } else if constexpr (h == 53) {
-                        p_rest(acc[1 - P][1], 1, u - 1);
-                    }
-                }
-                __builtin_amdgcn_sched_barrier(0);
-            });
-        });
-    };
-    using yes = std::true_type;
-    using no = std::false_type;
-    using P0 = std::integral_constant<int, 0>;
-    using P1 = std::integral_constant<int, 1>;
-
-    // prologue: units 0..2 in flight, the first three fragments of unit 0
-#pragma unroll 1
-    for (int pre = 0; pre < 3; ++pre)
-        if (pre < nunits) {
-            fill_unit(pre);
-#pragma unroll
-            for (int p = 0; p < 8; ++p) fill(pre, p);
-        }
-    if (nunits > 2) asm volatile("s_waitcnt vmcnt(16)" ::: "memory");           // unit 0 has landed
-    else if (nunits > 1) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-    RB_RD(fr[0], 0, 0);
-    RB_RD(fr[1], 1, 0);
-    RB_RD(fr[2], 2, 0);
-    RB_WAIT(2, fr[0]);
-    if constexpr (XM & 4) {
-#pragma unroll
-        for (int q = 0; q < 2; ++q)
-#pragma unroll
-            for (int i = 0; i < 16; ++i) acc[0][q][i] = acc[1][q][i] = 0.f;
-    }
-
-    body(no{}, P0{}, 0);
-    int u = 1;
-    for (; u + 1 < nunits; u += 2) {
-        body(yes{}, P1{}, u);
-        body(yes{}, P0{}, u + 1);
-    }
-    const bool odd_tail = u < nunits;
-    if (odd_tail) body(yes{}, P1{}, u);
-    // epilogue of the last unit (the only one with padded names), not hidden behind anything
-    {
-        asm volatile("s_nop 15\n\ts_nop 7" : "+v"(acc[0][0]), "+v"(acc[0][1]), "+v"(acc[1][0]), "+v"(acc[1][1]));   // MFMA -> VALU read
-        const int lu = nunits - 1;
-#pragma unroll
-        for (int q = 0; q < 2; ++q) {
-            f32x16 la = odd_tail ? acc[1][q] : acc[0][q];
-#pragma unroll
-            for (int i = 0; i < 16; ++i)
-                if ((long long)name_of(lu, i) >= v) la[i] = RB_NEG;
-#pragma unroll
-            for (int i = 0; i < 16; ++i) p_top2(la, q, i);
-            tk[q] = widen(m1[q], lu);
-            p_ins_all(q);
-            p_rest(la, q, lu);
-            if (SOFTMAX) {
-                p_sm_begin(q);
-#pragma unroll
-                for (int i = 0; i < 16; i += 2)
-                    if ((long long)name_of(lu, i) < v) {       // positions i, i+1 are names 4hh + {0,1} / {2,3} (+8..): mask per value
-                        const float e0 = __builtin_amdgcn_exp2f(fmaf(la[i], c2, nmc[q]));
-                        const float e1 = (long long)name_of(lu, i + 1) < v ? __builtin_amdgcn_exp2f(fmaf(la[i + 1], c2, nmc[q])) : 0.f;
-                        smz[q] += e0 + e1;
-                    }
-            }
-        }
-    }
-#pragma unroll
-    for (int q = 0; q < 2; ++q) {
-        const long long img = (long long)blockIdx.x * 256 + wave * 64 + q * 32 + r;
-        if (img < n) {
-            float* cv = cand_val + (img * 2 + hh) * TM;
-            int* ci = cand_idx + (img * 2 + hh) * TM;
-#pragma unroll
-            for (int j = 0; j < TM; ++j) {
-                const int idx = __double2loint(L[q][j]);
-                const bool ok = L[q][j] > -INFINITY && (long long)idx < v;
-                cv[j] = ok ? (float)L[q][j] * scale : -INFINITY;
-                ci[j] = ok ? idx : -1;
-            }
-            if (SOFTMAX) {
-                stats[(img * 2 + hh) * 2] = smm[q] * scale;
-                stats[(img * 2 + hh) * 2 + 1] = smz[q];
-            }
-        }
-    }
-#undef RB_RD
-#undef RB_WAIT
-#undef RB_MFMA
-#undef RB_MFMA0
-}
-
-#endif  // SCD_ABLATE
 
 // ------------------------------------------------------------------------------------------------
-// Eight-wave row-block kernel (round 3; default at d == 512).  Same unit structure, ring, keys and lists as sim_topk_rb_kernel,
+// Eight-wave row-block kernel (round 3; default at d == 512).  Same unit structure, ring, keys and lists as the four-wave kernel above described,
 // but TWO waves per SIMD with 32 images each (128 AGPRs of B fragments + <= 128 VGPRs): the four-wave kernel's lone wave per SIMD
 // has to issue everything itself - 64 MFMAs (8 issue cycles each), ~170-290 vector instructions of epilogue, 32 fragment reads,
 // 8 ring fills (60-100 cycles of issue each) and the waits - in ONE in-order stream per unit, ~4,100-4,700 cycles against 2,048
@@ -637,7 +346,7 @@ __device__ __forceinline__ float rb_swap32(float v, int lane) {         // the v
     return __uint_as_float((lane & 32) ? p[0] : p[1]);
 }
 #define RB8_EMARGIN 4.2f                   /* sim_refine_kernel certifies against (other half's entry KS) - 3.9 E: keep it below this */
-template <bool SOFTMAX, int TM, int KS, int XM = 0>
+template <bool SOFTMAX, int TM, int KS>
 __global__ void __launch_bounds__(512) sim_topk_rb8_kernel(const half_t* __restrict__ F, const half_t* __restrict__ Wt_all, long long n,
                                                            long long v_all, float scale, float* __restrict__ cand_val,
                                                            int* __restrict__ cand_idx, float* __restrict__ stats,
@@ -792,11 +501,10 @@ __global__ void __launch_bounds__(512) sim_topk_rb8_kernel(const half_t* __restr
     auto p_sm_add = [&](const f32x16& a, int i) { smz += __builtin_amdgcn_exp2f(fmaf(a[i], c2, nmc)); };
 
     f32x16 acc[2];
-    f32x4 acc16[4] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
     half8 fr[4];
     auto body = [&](auto has_prev, auto parity, int u) {
         constexpr int P = decltype(parity)::value;
-        constexpr bool EPI = decltype(has_prev)::value && !(XM & 1);
+        constexpr bool EPI = decltype(has_prev)::value;
         // my fills of unit u+1 have landed (those of u+2 may fly); after the barrier everybody's have, and slot (u-1)&3 is free
         if (u + 2 < nunits) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
         else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -817,31 +525,23 @@ __global__ void __launch_bounds__(512) sim_topk_rb8_kernel(const half_t* __restr
             if (s < 29 || more) RB_WAIT(2, fr[(s + 1) & 3]);
             else if (s == 29) RB_WAIT(1, fr[(s + 1) & 3]);
             else if (s == 30) RB_WAIT(0, fr[(s + 1) & 3]);
-            if constexpr (XM & 256) {                              // timing only: the same stream on 16x16x32 MFMAs (two per fragment)
-                asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, %0" : "+v"(acc16[2 * (s & 1)]) : "v"(fr[s & 3]), "a"(bf[s]));
-                asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, %0" : "+v"(acc16[2 * (s & 1) + 1]) : "v"(fr[s & 3]), "a"(bf[s ^ 1]));
-            } else if constexpr (!(XM & 4)) {
-                if constexpr (XM & 16) __builtin_amdgcn_s_setprio(1);
-                if (s == 0) RB_MFMA0(acc[P], fr[s & 3], bf[s]);
-                else RB_MFMA(acc[P], fr[s & 3], bf[s]);
-                if constexpr (XM & 16) __builtin_amdgcn_s_setprio(0);
-            }
-            if constexpr (!(XM & 2))
-                if ((s & 7) == 7 && fills) fill(s >> 3);
+            if (s == 0) RB_MFMA0(acc[P], fr[s & 3], bf[s]);
+            else RB_MFMA(acc[P], fr[s & 3], bf[s]);
+            if ((s & 7) == 7 && fills) fill(s >> 3);
             if constexpr (EPI) {
                 if constexpr (s >= 2 && s < 10) {
                     p_top2(acc[1 - P], 2 * (s - 2));
                     p_top2(acc[1 - P], 2 * (s - 2) + 1);
                 } else if constexpr (s == 10) {
-                    if constexpr (!(XM & 32)) tk = widen(m1, u - 1);
+                    tk = widen(m1, u - 1);
                     if (SOFTMAX) p_sm_begin();
                 } else if constexpr (s >= 11 && s < 27) {
-                    if constexpr (s - 11 < TM && !(XM & 32)) p_ins(s - 11);
+                    if constexpr (s - 11 < TM) p_ins(s - 11);
                     if (SOFTMAX) p_sm_add(acc[1 - P], s - 11);
                 } else if constexpr (s == 27) {
-                    if constexpr (!(XM & 96)) p_rest(acc[1 - P], u - 1);
+                    p_rest(acc[1 - P], u - 1);
                 } else if constexpr (s == 28 && P == 0) {
-                    if constexpr (!(XM & 128)) p_share();
+                    p_share();
                 }
             }
             __builtin_amdgcn_sched_barrier(0);
@@ -869,10 +569,6 @@ __global__ void __launch_bounds__(512) sim_topk_rb8_kernel(const half_t* __restr
     RB_RD(fr[1], 1, 0);
     RB_RD(fr[2], 2, 0);
     RB_WAIT(2, fr[0]);
-    if constexpr (XM & (4 | 256)) {
-#pragma unroll
-        for (int i = 0; i < 16; ++i) acc[0][i] = acc[1][i] = 0.f;
-    }
 
     body(no{}, P0{}, 0);
     int u = 1;
@@ -904,10 +600,6 @@ __global__ void __launch_bounds__(512) sim_topk_rb8_kernel(const half_t* __restr
     };
     if (odd_tail) tail(P1{});
     else tail(P0{});
-    if constexpr (XM & 256) {
-        asm volatile("s_nop 15" : "+v"(acc16[0]), "+v"(acc16[1]), "+v"(acc16[2]), "+v"(acc16[3]));
-        smz += acc16[0][0] + acc16[1][0] + acc16[2][0] + acc16[3][0];
-    }
     if (img < n) {
         const long long orow = (long long)part * part_rows + (img - out_row0);
         float* cv = cand_val + (orow * 2 + hh) * TM;
@@ -987,7 +679,7 @@ __device__ __forceinline__ float rc_swap16(float v, int lane) {         // the v
     const auto p = __builtin_amdgcn_permlane16_swap(u, u, false, false);
     return __uint_as_float((lane & 16) ? p[0] : p[1]);
 }
-template <bool SOFTMAX, int TM, int KS, int XM = 0>
+template <bool SOFTMAX, int TM, int KS>
 __global__ void __launch_bounds__(512) sim_topk_rc_kernel(const half_t* __restrict__ F, const half_t* __restrict__ Wt, long long n,
                                                           long long v, float scale, float* __restrict__ cand_val,
                                                           int* __restrict__ cand_idx, float* __restrict__ stats,
@@ -1158,7 +850,7 @@ __global__ void __launch_bounds__(512) sim_topk_rc_kernel(const half_t* __restri
     using P1 = std::integral_constant<int, 1>;
     auto body = [&](auto has_prev, auto parity, int u) {
         constexpr int P = decltype(parity)::value;
-        constexpr bool EPI = decltype(has_prev)::value && !(XM & 1);
+        constexpr bool EPI = decltype(has_prev)::value;
         using PREV = std::integral_constant<int, 1 - P>;
         if (u + 2 < nunits) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
         else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -1169,7 +861,7 @@ __global__ void __launch_bounds__(512) sim_topk_rc_kernel(const half_t* __restri
         if (fills) fill_unit(u + 3);
         static_for<0, 32>([&](auto sc_) {
             // fragment step s = 2 ks + tj: two MFMAs (image tiles 0, 1).  Reads run three fragments ahead; the wait of step s
-            // retires the fragment of step s + 1 (a whole step before its first use, see sim_topk_rb_kernel)
+            // retires the fragment of step s + 1 (a whole step before its first use)
             constexpr int s = decltype(sc_)::value, ks = s >> 1, tj = s & 1;
             if (s == 29) {
                 const unsigned delta = ((u + 1) & 3) ? (unsigned)UB : (unsigned)(-3 * UB);      // wave-uniform
@@ -1183,12 +875,9 @@ __global__ void __launch_bounds__(512) sim_topk_rc_kernel(const half_t* __restri
             else if (s == 30) RC_WAIT(0, fr[(s + 1) & 3]);
             static_for<0, 2>([&](auto tc) {
                 constexpr int ti = decltype(tc)::value, h = 2 * s + ti;
-                if constexpr (!(XM & 4)) {
-                    if (ks == 0) RC_MFMA0(acc[P][tj][ti], fr[s & 3], bf[ks][ti]);
-                    else RC_MFMA(acc[P][tj][ti], fr[s & 3], bf[ks][ti]);
-                }
-                if constexpr (!(XM & 2))
-                    if ((h & 15) == 15 && fills) fill(h >> 4);
+                if (ks == 0) RC_MFMA0(acc[P][tj][ti], fr[s & 3], bf[ks][ti]);
+                else RC_MFMA(acc[P][tj][ti], fr[s & 3], bf[ks][ti]);
+                if ((h & 15) == 15 && fills) fill(h >> 4);
                 if constexpr (EPI) {
                     // tile t2 = h / 20 (h < 40): its slots are h0 = h - 20 t2 - 4: 0..7 key pair, 8 widen, 9.. list entries and,
                     // 9..16, softmax terms, 18 the second-key path
@@ -1204,14 +893,14 @@ __global__ void __launch_bounds__(512) sim_topk_rc_kernel(const half_t* __restri
                         if constexpr (h0 >= 9 && h0 < 17) {
                             if (SOFTMAX) p_sm_add(acc[1 - P][(h0 - 9) >> 2][t2][(h0 - 9) & 3], t2);
                         }
-                        if constexpr (h0 == 18 && !(XM & 64)) {
+                        if constexpr (h0 == 18) {
                             if constexpr (t2 == 0) p_rest(PREV{}, P0{}, u - 1);
                             else p_rest(PREV{}, P1{}, u - 1);
                         }
                     }
                     // (two slots: in one, hipcc packs the two subtractions into a v_pk_add_f32 whose (e4, e4) operand it then spills)
-                    if constexpr (h == 48 && P == 0 && !(XM & 128)) p_share(0);
-                    if constexpr (h == 50 && P == 0 && !(XM & 128)) p_share(1);
+                    if constexpr (h == 48 && P == 0) p_share(0);
+                    if constexpr (h == 50 && P == 0) p_share(1);
                 }
                 __builtin_amdgcn_sched_barrier(0);
             });
@@ -1233,12 +922,6 @@ __global__ void __launch_bounds__(512) sim_topk_rc_kernel(const half_t* __restri
     RC_RD(fr[1], 0, 16384);
     RC_RD(fr[2], 1, 0);
     RC_WAIT(2, fr[0]);
-    if constexpr (XM & 4) {
-#pragma unroll
-        for (int q = 0; q < 8; ++q)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) acc[q >> 2][(q >> 1) & 1][q & 1][e] = 0.f;
-    }
 
     body(no{}, P0{}, 0);
     int u = 1;
@@ -1974,14 +1657,9 @@ static int sim_topk_impl(scd_handle h, const void* F, const void* Wt, int64_t n,
     // SCD_SIM_RB: 8 (default) = the eight-wave 32x32x16 kernel with eight entries per half list for k >= 2; 16 = 16x16x32 tiles for
     // k <= 3 (2-3 % faster on unstructured features, but its 16 candidates per image are the best four of four QUARTER lists: on
     // features whose top logits crowd inside the error bound - the bench's synthetic images: 100 planted names within ~0.5 - a hundred
-    // rows per call fail their certificate and the exact pass costs more than the tiles save); with -DSCD_ABLATE also 1 = four-wave
-    // predecessor, 0 = tile kernel, and SCD_SIM_X = timing ablations (results are wrong)
+    // rows per call fail their certificate and the exact pass costs more than the tiles save)
     static const int use_rb_env = getenv("SCD_SIM_RB") ? atoi(getenv("SCD_SIM_RB")) : 8;
-#ifdef SCD_ABLATE
-    const int use_rb = use_rb_env;
-#else
     const int use_rb = use_rb_env == 16 ? 16 : 8;
-#endif
     const bool sm = mode == SCD_SIM_SOFTMAX;
     if (use_rb && d == 512 && v < (1ll << 28)) {
         // row-block kernels (the CLIP width): units of 32 names x K = 512, epilogue hidden behind the next unit's MFMAs
@@ -1992,7 +1670,7 @@ static int sim_topk_impl(scd_handle h, const void* F, const void* Wt, int64_t n,
         { const int rc_ = sim_exact_launch<SM>(f, wt, d, v, scale, k, hdr, fb, expart, (long long*)idx_out, val_out, st); if (rc_) return rc_; }
 #define RC_GO(SM, TMV, KSV)                                                                                                     \
     {                                                                                                                           \
-        { const int rc_ = scd_set_max_lds((const void*)sim_topk_rc_kernel<SM, TMV, KSV, 0>, 131072); if (rc_) return rc_; }         \
+        { const int rc_ = scd_set_max_lds((const void*)sim_topk_rc_kernel<SM, TMV, KSV>, 131072); if (rc_) return rc_; }            \
         sim_topk_rc_kernel<SM, TMV, KSV><<<g1, 512, 131072, st>>>(f, wt, n, v, scale, cval, cidx, stats, bnd, &hdr->wmax2_bits); \
         sim_refine4_kernel<SM, 8><<<(unsigned)scd_cdiv(n, 16), 256, 0, st>>>(f, wt, n, v, scale, k, cval, cidx, stats, hdr, fb, (long long*)idx_out, val_out, -1, bnd, 4); \
         { const int rc_ = sim_exact_launch<SM>(f, wt, d, v, scale, k, hdr, fb, expart, (long long*)idx_out, val_out, st); if (rc_) return rc_; } \
@@ -2010,7 +1688,7 @@ static int sim_topk_impl(scd_handle h, const void* F, const void* Wt, int64_t n,
         float* sp_st = (float*)(sp + 2 * scd_align(SIM_SPLIT_ROWS * 2 * TOPM * 4));
 #define RB8_GO(SM, TMV, KSV)                                                                                                    \
     {                                                                                                                           \
-        { const int rc_ = scd_set_max_lds((const void*)sim_topk_rb8_kernel<SM, TMV, KSV, 0>, 131072); if (rc_) return rc_; }        \
+        { const int rc_ = scd_set_max_lds((const void*)sim_topk_rb8_kernel<SM, TMV, KSV>, 131072); if (rc_) return rc_; }           \
         if (!split) sim_topk_rb8_kernel<SM, TMV, KSV><<<g1, 512, 131072, st>>>(f, wt, n, v, scale, cval, cidx, stats, &hdr->wmax2_bits); \
         else {                                                                                                                  \
             const long long row0 = (long long)(g1 - rem) * 256, prow = (long long)rem * 256;                                   \
@@ -2022,39 +1700,6 @@ static int sim_topk_impl(scd_handle h, const void* F, const void* Wt, int64_t n,
         }                                                                                                                       \
         RB_TAIL(SM, TMV, KSV)                                                                                                   \
     }
-#ifdef SCD_ABLATE
-#define RB_GO(SM, TMV)                                                                                                          \
-    {                                                                                                                           \
-        { const int rc_ = scd_set_max_lds((const void*)sim_topk_rb_kernel<SM, TMV, 0>, 131072); if (rc_) return rc_; }              \
-        sim_topk_rb_kernel<SM, TMV><<<g1, 256, 131072, st>>>(f, wt, n, v, scale, cval, cidx, stats);                             \
-        RB_TAIL(SM, TMV, -1)                                                                                                    \
-    }
-        static const int sim_x_rb = SCD_ABLATE_ENV("SCD_SIM_X", 0);
-        if (sim_x_rb) {                                          // timing ablations of the raw kernels (tools/sim_bench.py): kernel only, no refine
-            switch (sim_x_rb + (use_rb == 8 ? 1000 : use_rb == 16 ? 2000 : 0)) {
-#define RC_X(X) case 2000 + X: { const int rc_ = scd_set_max_lds((const void*)sim_topk_rc_kernel<false, 5, 2, X>, 131072); if (rc_) return rc_; } \
-                        sim_topk_rc_kernel<false, 5, 2, X><<<g1, 512, 131072, st>>>(f, wt, n, v, scale, cval, cidx, stats, bnd, &hdr->wmax2_bits); break;
-#define RB_X(X) case X: { const int rc_ = scd_set_max_lds((const void*)sim_topk_rb_kernel<false, 8, X>, 131072); if (rc_) return rc_; } \
-                        sim_topk_rb_kernel<false, 8, X><<<g1, 256, 131072, st>>>(f, wt, n, v, scale, cval, cidx, stats); break;
-#define RB8_X(X) case 1000 + X: { const int rc_ = scd_set_max_lds((const void*)sim_topk_rb8_kernel<false, 8, 2, X>, 131072); if (rc_) return rc_; } \
-                        sim_topk_rb8_kernel<false, 8, 2, X><<<g1, 512, 131072, st>>>(f, wt, n, v, scale, cval, cidx, stats, &hdr->wmax2_bits); break;
-                RC_X(1) RC_X(3) RC_X(64) RC_X(1024)
-                RB_X(1) RB_X(3) RB_X(4)
-                RB8_X(1) RB8_X(3) RB8_X(64) RB8_X(1024)
-#undef RC_X
-#undef RB_X
-#undef RB8_X
-            }
-            SCD_LAUNCH_CHECK();
-            return SCD_OK;
-        }
-        if (use_rb == 1) {
-            // k == 1: two half lists of 4; k >= 2: 8 (certification needs margin)
-            if (k == 1) { if (sm) RB_GO(true, 4) else RB_GO(false, 4) }
-            else { if (sm) RB_GO(true, 8) else RB_GO(false, 8) }
-        } else
-#undef RB_GO
-#endif
         if (use_rb == 16 && k <= 3) {
             // 16x16x32 tiles, four quarter lists per image: TM = k + 2 entries each, the best four leave the kernel
             if (k == 1) { if (sm) RC_GO(true, 3, 0) else RC_GO(false, 3, 0) }

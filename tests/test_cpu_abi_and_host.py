@@ -45,14 +45,20 @@ def test_no_torch_types_in_abi():
 
 
 def test_default_library_has_no_ablation_switches():
-    """Timing ablations (kernels with pieces removed: wrong results) and the A/B kernels of earlier rounds exist only in the
-    -DSCD_ABLATE build (`python -m scd_amd.build --ablate`): the shipped library neither reads those variables nor contains the
-    code behind them."""
+    """Timing ablations (kernels with pieces removed: wrong results) and the A/B kernels of earlier rounds were removed together
+    with the -DSCD_ABLATE build that held them: the library neither reads those variables nor contains the code behind them, and
+    the sources carry no trace of that build."""
     blob = open(os.path.join(ROOT, "scd_amd", "lib", "libscd_hip.so"), "rb").read()
     for name in (b"SCD_GEMM_X", b"SCD_SIM_X", b"SCD_ATTN_X", b"SCD_ESTEP_DBG", b"SCD_ESTEP_REFINE_SPLIT", b"SCD_GEMM_MFMA", b"SCD_GEMM_TILE"):
         assert name not in blob, name
     for kern in (b"gemm_w8_kernel", b"gemm_dma16_kernel", b"sim_topk_w4_kernel", b"sim_topk_rb_kernel"):
         assert kern not in blob, kern
+    csrc = os.path.join(ROOT, "scd_amd", "csrc")
+    assert not os.path.exists(os.path.join(csrc, "ablate"))
+    for dp, _, fs in os.walk(os.path.join(ROOT, "scd_amd")):
+        for f in fs:
+            if f.endswith(".py") or (dp.startswith(csrc) and f.endswith((".hip", ".cpp", ".h"))):
+                assert "SCD_ABLATE" not in open(os.path.join(dp, f)).read(), os.path.join(dp, f)     # covers SCD_ABLATE_ENV
 
 
 def test_product_does_not_import_oracle():

@@ -790,8 +790,8 @@ def test_sim_topk_vocabulary_norm_is_computed_once_and_follows_the_tensor(ops):
 
 
 def test_ablation_variables_change_nothing_in_the_default_library():
-    """SCD_GEMM_X / SCD_SIM_X / SCD_ATTN_X / SCD_ESTEP_DBG removed kernel pieces (wrong results) in rounds 1-2; the default build
-    ignores them: a child process with all of them set returns the oracle's top-k and labels."""
+    """SCD_GEMM_X / SCD_SIM_X / SCD_ATTN_X / SCD_ESTEP_DBG removed kernel pieces (wrong results) in rounds 1-2; the library no
+    longer knows them: a child process with all of them set returns the oracle's top-k and labels."""
     import subprocess
     import sys
     code = """
