@@ -422,6 +422,25 @@ int scd_attention_single_query_f16(scd_handle h, const void* kv, const void* q, 
 /* building block exposed for tests: C[m,n] = A[m,k] @ W[n,k]^T (+bias)(act)(+residual), fp16 in/out, fp32 accumulate */
 int scd_gemm_f16(scd_handle h, const void* A, const void* W, const float* bias, const void* residual, void* C,
                  int64_t m, int n, int k, int act, void* stream);
+/* building blocks exposed for tests: the rest of the GEMM family the encoder blocks run, each through the launcher the towers call.
+ * scd_gemm_ln_apply_f16: C = act(LayerNorm(A) W^T + b) in the folded form (QKV / fc1): Wf, biasf, colsum as scd_fold_ln_f16 makes them,
+ *   stats_in int64 [m][2] = {sum * 2^24, sum of squares * 2^20} of A's rows; rs float [m][2] is scratch ({rstd, -mean * rstd} on return),
+ *   zero_out (or NULL) a second [m][2] statistics buffer that is cleared.  m % 256 = n % 256 = k % 64 = 0.
+ * scd_gemm_res_stats_f16: C = A W^T + bias + residual (proj / fc2; C may be the residual buffer) and stats_out[m] += the same fixed-point
+ *   sums of the stored rows of C (the caller clears stats_out).  bias and residual are required, act must be 0.
+ * scd_fold_ln_f16: Wf[n][k] = fp16(W[n][k] gamma[k]), colsum[n] = sum_k Wf[n][k], biasf[n] = bias[n] + sum_k beta[k] W[n][k].
+ * scd_gemm_img_f16: the patch-16 embedding GEMM fed from the fp16 image batch [batch][3][image][image]: row b * (image/16)^2 + p of C
+ *   [m][n] = patch (b, p) (k = c * 256 + i * 16 + j) times W[n][768]^T; m % 256 = 0, m >= batch * (image/16)^2 (rows beyond: scratch).
+ * scd_layernorm_f16: out[r] = fp16(LayerNorm(x[row_index ? row_index[r] : r]) gamma + beta), width a multiple of 256, at most 1024. */
+int scd_gemm_ln_apply_f16(scd_handle h, const void* A, const void* Wf, const float* biasf, const float* colsum, const int64_t* stats_in,
+                          float* rs, int64_t* zero_out, void* C, int64_t m, int n, int k, float eps, int act, void* stream);
+int scd_gemm_res_stats_f16(scd_handle h, const void* A, const void* W, const float* bias, const void* residual, void* C,
+                           int64_t* stats_out, int64_t m, int n, int k, int act, void* stream);
+int scd_fold_ln_f16(scd_handle h, const void* W, const float* gamma, const float* beta, const float* bias, int n, int k, void* Wf,
+                    float* colsum, float* biasf, void* stream);
+int scd_gemm_img_f16(scd_handle h, const void* pixels, const void* W, void* C, int64_t m, int n, int batch, int image, void* stream);
+int scd_layernorm_f16(scd_handle h, const void* x, const int* row_index, int64_t rows, int width, float eps, const float* gamma,
+                      const float* beta, void* out, void* stream);
 
 /* ---- image preprocessing: CLIP's `preprocess` (main_unsup.py:237,271, applied by the DataLoader at :271-289) on decoded images -
  *      torchvision Resize(size, BICUBIC) on a PIL RGB image (Pillow Resample.c, uint8, separable, int32 taps with 22 fraction bits),

@@ -137,6 +137,13 @@ SIGNATURES = {
     "scd_clip_encode_text": (_i, [_vp, _vp, _vp, _i, _vp, _i, _vp, _sz, _vp]),
     "scd_clip_encode_text_len": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _vp, _sz, _vp]),
     "scd_gemm_f16": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _i, _vp]),
+    # h, A, Wf, biasf, colsum, stats_in, rs, zero_out, C, m, n, k, eps, act, stream
+    "scd_gemm_ln_apply_f16": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _f, _i, _vp]),
+    # h, A, W, bias, residual, C, stats_out, m, n, k, act, stream
+    "scd_gemm_res_stats_f16": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _i, _vp]),
+    "scd_fold_ln_f16": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp]),
+    "scd_gemm_img_f16": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _i, _vp]),
+    "scd_layernorm_f16": (_i, [_vp, _vp, _vp, _i64, _i, _f, _vp, _vp, _vp, _vp]),
     "scd_attention_f16": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "scd_attention_single_query_f16": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "scd_image_geometry": (_i, [_i, _i, _i, _i, _vp]),

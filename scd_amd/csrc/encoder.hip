@@ -1486,3 +1486,61 @@ extern "C" int scd_attention_single_query_f16(scd_handle h, const void* kv, cons
     SCD_LAUNCH_CHECK();
     return SCD_OK;
 }
+
+// ------------------------------------------------------------------------------------------------ GEMM-family entry points (tests)
+// Each runs the launcher run_blocks / scd_encoder_create / run_head runs, on caller buffers; what the launchers reject is rejected here
+// before anything is launched.
+extern "C" int scd_gemm_ln_apply_f16(scd_handle h, const void* A, const void* Wf, const float* biasf, const float* colsum,
+                                     const int64_t* stats_in, float* rs, int64_t* zero_out, void* C, int64_t m, int n, int k, float eps,
+                                     int act, void* stream) {
+    SCD_DEVICE_ENTRY(h, "scd_gemm_ln_apply_f16");
+    SCD_REQUIRE(A && Wf && biasf && colsum && stats_in && rs && C, "scd_gemm_ln_apply_f16: null argument");
+    SCD_REQUIRE(m > 0 && m % 256 == 0 && n > 0 && n % 256 == 0 && k > 0 && k % 64 == 0 && m < (1ll << 31),
+                "scd_gemm_ln_apply_f16: shape m=%lld n=%d k=%d must be multiples of 256/256/64", (long long)m, n, k);
+    SCD_REQUIRE(C != A, "scd_gemm_ln_apply_f16: C must not alias A");
+    SCD_REQUIRE(act == SCD_ACT_NONE || act == SCD_ACT_QUICKGELU || act == SCD_ACT_GELU, "scd_gemm_ln_apply_f16: bad activation %d", act);
+    hipStream_t st = (hipStream_t)stream;
+    int rc = scd_gemm_ln_finish((const long long*)stats_in, m, 1.0f / (float)k, eps, rs, (long long*)zero_out, st);
+    if (rc) return rc;
+    scd_gemm_ln ln{(const long long*)stats_in, colsum, 1.0f / (float)k, eps, nullptr, (long long*)zero_out, rs};
+    return scd_gemm_launch_ln((const half_t*)A, (const half_t*)Wf, biasf, nullptr, (half_t*)C, m, n, k, act, &ln, st);
+}
+
+extern "C" int scd_gemm_res_stats_f16(scd_handle h, const void* A, const void* W, const float* bias, const void* residual, void* C,
+                                      int64_t* stats_out, int64_t m, int n, int k, int act, void* stream) {
+    SCD_DEVICE_ENTRY(h, "scd_gemm_res_stats_f16");
+    SCD_REQUIRE(stats_out, "scd_gemm_res_stats_f16: null statistics buffer");
+    SCD_REQUIRE(n > 0 && k > 0, "scd_gemm_res_stats_f16: bad shape n=%d k=%d", n, k);
+    scd_gemm_ln ln{nullptr, nullptr, 0.f, 0.f, (long long*)stats_out, nullptr, nullptr};
+    return scd_gemm_launch_ln((const half_t*)A, (const half_t*)W, bias, (const half_t*)residual, (half_t*)C, m, n, k, act, &ln,
+                              (hipStream_t)stream);
+}
+
+extern "C" int scd_fold_ln_f16(scd_handle h, const void* W, const float* gamma, const float* beta, const float* bias, int n, int k,
+                               void* Wf, float* colsum, float* biasf, void* stream) {
+    SCD_DEVICE_ENTRY(h, "scd_fold_ln_f16");
+    SCD_REQUIRE(W && gamma && beta && bias && Wf && colsum && biasf && Wf != W, "scd_fold_ln_f16: null or aliased argument");
+    SCD_REQUIRE(n > 0 && k > 0, "scd_fold_ln_f16: bad shape n=%d k=%d", n, k);
+    fold_ln_kernel<<<(n + 3) / 4, 256, 0, (hipStream_t)stream>>>((const half_t*)W, gamma, beta, bias, n, k, (half_t*)Wf, colsum, biasf);
+    SCD_LAUNCH_CHECK();
+    return SCD_OK;
+}
+
+extern "C" int scd_gemm_img_f16(scd_handle h, const void* pixels, const void* W, void* C, int64_t m, int n, int batch, int image,
+                                void* stream) {
+    SCD_DEVICE_ENTRY(h, "scd_gemm_img_f16");
+    SCD_REQUIRE(image > 0 && n > 0 && m > 0, "scd_gemm_img_f16: bad shape (m=%lld n=%d image=%d)", (long long)m, n, image);
+    return scd_gemm_launch_img((const half_t*)pixels, (const half_t*)W, (half_t*)C, m, n, batch, image, (hipStream_t)stream);
+}
+
+extern "C" int scd_layernorm_f16(scd_handle h, const void* x, const int* row_index, int64_t rows, int width, float eps, const float* gamma,
+                                 const float* beta, void* out, void* stream) {
+    SCD_DEVICE_ENTRY(h, "scd_layernorm_f16");
+    SCD_REQUIRE(x && gamma && beta && out && out != x, "scd_layernorm_f16: null or aliased argument");
+    SCD_REQUIRE(rows > 0 && width > 0 && width % 256 == 0 && width <= 1024,
+                "scd_layernorm_f16: rows %lld, width %d (a multiple of 256, at most 1024)", (long long)rows, width);
+    layernorm_kernel<<<(unsigned)scd_cdiv(rows, 4), 256, 0, (hipStream_t)stream>>>((const half_t*)x, row_index, rows, width, eps, gamma, beta,
+                                                                                   (half_t*)out);
+    SCD_LAUNCH_CHECK();
+    return SCD_OK;
+}

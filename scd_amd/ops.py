@@ -904,13 +904,117 @@ class Comm:
 
 
 # ----------------------------------------------------------------------------- encoders
-def gemm_f16(a, w, bias=None, residual=None, act=0):
+def gemm_f16(a, w, bias=None, residual=None, act=0, out=None):
+    """C = act(a @ w^T + bias) + residual (scd_gemm_f16).  out: the fp16 [m, n] buffer to write - it may be `residual` itself, as in
+    the encoder blocks (x = x + proj(...)); a fresh one is allocated when None."""
     _need_cuda(a, w)
     m, k = a.shape
     n = w.shape[0]
-    c = torch.empty((m, n), dtype=torch.float16, device=a.device)
-    check(_L().scd_gemm_f16(handle(), ptr(a), ptr(w), ptr(bias), ptr(residual), ptr(c), m, n, k, int(act), stream_ptr()))
-    return c
+    if out is None:
+        out = torch.empty((m, n), dtype=torch.float16, device=a.device)
+    assert out.dtype == torch.float16 and out.is_contiguous() and out.shape == (m, n) and out.device == a.device
+    check(_L().scd_gemm_f16(handle(), ptr(a), ptr(w), ptr(bias), ptr(residual), ptr(out), m, n, k, int(act), stream_ptr()))
+    return out
+
+
+def _f16c(*ts):
+    for t in ts:
+        assert t.dtype == torch.float16 and t.is_contiguous() and t.is_cuda
+
+
+def _f32c(*ts):
+    for t in ts:
+        assert t.dtype == torch.float32 and t.is_contiguous() and t.is_cuda
+
+
+def gemm_ln_apply_f16(a, wf, biasf, colsum, stats_in, eps, act=0, rs=None, zero_out=None, out=None):
+    """The LayerNorm-folded QKV / fc1 GEMM (scd_gemm_ln_apply_f16: scd_gemm_ln_finish, then gemm_w4_kernel LN = 1).  stats_in int64
+    [m, 2] fixed-point row sums of a; rs float32 [m, 2] scratch ({rstd, -mean * rstd} afterwards); zero_out int64 [m, 2] is cleared."""
+    _need_cuda(a, wf)
+    m, k = a.shape
+    n = wf.shape[0]
+    _f16c(a, wf)
+    _f32c(biasf, colsum)
+    assert wf.shape == (n, k) and biasf.shape == (n,) and colsum.shape == (n,)
+    assert stats_in.dtype == torch.int64 and stats_in.is_contiguous() and stats_in.shape == (m, 2)
+    if rs is None:
+        rs = torch.empty((m, 2), dtype=torch.float32, device=a.device)
+    _f32c(rs)
+    assert rs.shape == (m, 2)
+    if zero_out is not None:
+        assert zero_out.dtype == torch.int64 and zero_out.is_contiguous() and zero_out.shape == (m, 2)
+    if out is None:
+        out = torch.empty((m, n), dtype=torch.float16, device=a.device)
+    _f16c(out)
+    assert out.shape == (m, n)
+    check(_L().scd_gemm_ln_apply_f16(handle(), ptr(a), ptr(wf), ptr(biasf), ptr(colsum), ptr(stats_in), ptr(rs), ptr(zero_out), ptr(out),
+                                     m, n, k, float(eps), int(act), stream_ptr()))
+    return out
+
+
+def gemm_res_stats_f16(a, w, bias, residual, stats_out, out=None, act=0):
+    """The proj / fc2 GEMM of a LayerNorm-folded block (scd_gemm_res_stats_f16, gemm_w4_kernel LN = 2): out = a @ w^T + bias + residual
+    and stats_out[m] += {sum * 2^24, sum of squares * 2^20} of the stored row m.  out may be `residual` (in place, as the blocks run)."""
+    _need_cuda(a, w)
+    m, k = a.shape
+    n = w.shape[0]
+    _f16c(a, w, residual)
+    _f32c(bias)
+    assert w.shape == (n, k) and bias.shape == (n,) and residual.shape == (m, n)
+    assert stats_out.dtype == torch.int64 and stats_out.is_contiguous() and stats_out.shape == (m, 2)
+    if out is None:
+        out = torch.empty((m, n), dtype=torch.float16, device=a.device)
+    _f16c(out)
+    assert out.shape == (m, n)
+    check(_L().scd_gemm_res_stats_f16(handle(), ptr(a), ptr(w), ptr(bias), ptr(residual), ptr(out), ptr(stats_out), m, n, k, int(act),
+                                      stream_ptr()))
+    return out
+
+
+def fold_ln_f16(w, gamma, beta, bias):
+    """LayerNorm folded into the Linear that follows it (scd_fold_ln_f16, fold_ln_kernel): returns Wf fp16 [n, k], colsum and biasf
+    float32 [n]."""
+    _need_cuda(w)
+    n, k = w.shape
+    _f16c(w)
+    _f32c(gamma, beta, bias)
+    assert gamma.shape == (k,) and beta.shape == (k,) and bias.shape == (n,)
+    wf = torch.empty_like(w)
+    colsum = torch.empty(n, dtype=torch.float32, device=w.device)
+    biasf = torch.empty(n, dtype=torch.float32, device=w.device)
+    check(_L().scd_fold_ln_f16(handle(), ptr(w), ptr(gamma), ptr(beta), ptr(bias), n, k, ptr(wf), ptr(colsum), ptr(biasf), stream_ptr()))
+    return wf, colsum, biasf
+
+
+def gemm_img_f16(pixels, w, m=None):
+    """The patch-16 embedding GEMM fed from the image batch (scd_gemm_img_f16, gemm_w4_kernel IMG): pixels fp16 [batch, 3, image, image],
+    w fp16 [n, 768] -> fp16 [m, n], m = batch * (image / 16)^2 rounded up to 256 unless given; rows beyond the patches are scratch."""
+    _need_cuda(pixels, w)
+    _f16c(pixels, w)
+    batch, _, image, _ = pixels.shape
+    assert pixels.shape == (batch, 3, image, image) and w.shape[1] == 768
+    n = w.shape[0]
+    if m is None:
+        m = (batch * (image // 16) ** 2 + 255) // 256 * 256
+    out = torch.empty((m, n), dtype=torch.float16, device=w.device)
+    check(_L().scd_gemm_img_f16(handle(), ptr(pixels), ptr(w), ptr(out), int(m), n, batch, image, stream_ptr()))
+    return out
+
+
+def layernorm_f16(x, gamma, beta, eps, row_index=None):
+    """The encoders' row LayerNorm (scd_layernorm_f16, layernorm_kernel): out[r] = LN(x[row_index[r]]) (row_index int32 or None)."""
+    _need_cuda(x)
+    _f16c(x)
+    _f32c(gamma, beta)
+    width = x.shape[1]
+    assert gamma.shape == (width,) and beta.shape == (width,)
+    rows = x.shape[0]
+    if row_index is not None:
+        row_index = row_index.to(device=x.device, dtype=torch.int32).contiguous()
+        rows = row_index.shape[0]
+    out = torch.empty((rows, width), dtype=torch.float16, device=x.device)
+    check(_L().scd_layernorm_f16(handle(), ptr(x), ptr(row_index), rows, width, float(eps), ptr(gamma), ptr(beta), ptr(out), stream_ptr()))
+    return out
 
 
 def attention_f16(qkv, batch, T, heads, causal=False):
