@@ -65,6 +65,13 @@ int scd_sim_topk_prenorm(scd_handle h, const void* F, const void* Wt, int64_t n,
  * main_ptsup.py:78-99): idx_out int64 [n], val_out float32 [n] = scd_sim_topk with k = 1 on the raw logits (ws: scd_sim_topk_ws_bytes(n, d, v, 1)). */
 int scd_sim_argmax(scd_handle h, const void* F, const void* Wt, int64_t n, int d, int64_t v, float scale, int64_t* idx_out,
                    float* val_out, void* ws, size_t ws_bytes, void* stream);
+/* Which kernels the last scd_sim_topk / _prenorm / scd_sim_argmax call of this process launched (a bit set; for tests of the
+ * SCD_SIM_RB / SCD_SIM_SPLIT / SCD_SIM_REFINE4 switches): exactly one of RB8 (32x32x16 row blocks, d = 512), RC16 (16x16x32 row blocks,
+ * d = 512, k <= 3), TILE (d < 512), TILE768; SPLIT: the last round of row blocks was split over the vocabulary; REFINE4: the
+ * four-images-per-wave refine kernel.  0 before the first call. */
+enum { SCD_SIM_PATH_RB8 = 1, SCD_SIM_PATH_RC16 = 2, SCD_SIM_PATH_TILE = 4, SCD_SIM_PATH_TILE768 = 8, SCD_SIM_PATH_SPLIT = 16,
+       SCD_SIM_PATH_REFINE4 = 32 };
+int scd_sim_last_path(void);
 /* W [r,c] fp16 -> Wt [c,r]  (zeroshot_weights [512,V] -> name-major) */
 int scd_transpose_f16(scd_handle h, const void* in, int64_t r, int64_t c, void* out, void* stream);
 /* out[i,:] = Wt[idx[i],:]  (the `zeroshot_weights[:, nouns.index(n)]` gather, main_unsup.py:601-602) */

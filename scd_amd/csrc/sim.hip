@@ -1618,6 +1618,11 @@ extern "C" int scd_sim_vocab_norm(scd_handle h, const void* Wt, int64_t v, int d
     return SCD_OK;
 }
 
+// which kernels the last scd_sim_topk* call of this process launched (include/scd_hip.h SCD_SIM_PATH_*): lets a test of the environment
+// switches prove that the switched path ran
+static int g_sim_last_path = 0;
+extern "C" int scd_sim_last_path(void) { return g_sim_last_path; }
+
 static int sim_topk_impl(scd_handle h, const void* F, const void* Wt, int64_t n, int d, int64_t v, float scale, int k,
                          int mode, int64_t* idx_out, float* val_out, int32_t* fallback_rows_out, void* ws,
                          size_t ws_bytes, const void* wmax2, void* stream_) {
@@ -1700,13 +1705,18 @@ static int sim_topk_impl(scd_handle h, const void* F, const void* Wt, int64_t n,
         }                                                                                                                       \
         RB_TAIL(SM, TMV, KSV)                                                                                                   \
     }
+        g_sim_last_path = (use_rb == 16 && k <= 3) ? (SCD_SIM_PATH_RC16 | SCD_SIM_PATH_REFINE4)
+                                                   : (SCD_SIM_PATH_RB8 | (split ? SCD_SIM_PATH_SPLIT : 0) | (refine4 ? SCD_SIM_PATH_REFINE4 : 0));
         if (use_rb == 16 && k <= 3) {
             // 16x16x32 tiles, four quarter lists per image: TM = k + 2 entries each, the best four leave the kernel
             if (k == 1) { if (sm) RC_GO(true, 3, 0) else RC_GO(false, 3, 0) }
             else { if (sm) RC_GO(true, 5, 2) else RC_GO(false, 5, 2) }
         } else {
-            // entries per half list TM >= k + 2 (a row fails its certificate only when one half holds the image's TM + 1 best and two
-            // gaps among them are inside the error bound); KS + 1 >= k: the entry of the other half's list the shared threshold uses
+            // entries per half list: TM >= k + 2 for k <= 6 (a row then fails its certificate only when one half holds the image's TM + 1
+            // best and two gaps among them are inside the error bound).  For k = 7, 8 TM = 8 < k + 2: a row whose k + 1 best names share
+            // a half list cannot be certified whatever the gaps (the list's last entry is the k-th value or next to it) and takes the
+            // exact pass (docs/design/sim_topk.md, "what the tests pin").  KS + 1 >= k: the entry of the other half's list the shared
+            // threshold uses
             if (k == 1) { if (sm) RB8_GO(true, 4, 0) else RB8_GO(false, 4, 0) }
             else if (k <= 3) { if (sm) RB8_GO(true, 8, 2) else RB8_GO(false, 8, 2) }
             else if (k <= 5) { if (sm) RB8_GO(true, 8, 4) else RB8_GO(false, 8, 4) }
@@ -1722,6 +1732,7 @@ static int sim_topk_impl(scd_handle h, const void* F, const void* Wt, int64_t n,
     if (d == 768) {
         // the ViT-L/14 width: the four-wave tile kernel with twelve 64-deep sub-steps per tile (128 images x 128 names)
         const unsigned g4 = (unsigned)scd_cdiv(n, 128);
+        g_sim_last_path = SCD_SIM_PATH_TILE768;
         { const int rc_ = scd_set_max_lds((const void*)sim_topk_kernel<true, 4, 12>, 65536 + 16384); if (rc_) return rc_; }
         { const int rc_ = scd_set_max_lds((const void*)sim_topk_kernel<false, 4, 12>, 65536 + 16384); if (rc_) return rc_; }
         if (sm) {
@@ -1738,6 +1749,7 @@ static int sim_topk_impl(scd_handle h, const void* F, const void* Wt, int64_t n,
         return SCD_OK;
     }
     // d < 512: the eight-wave tile kernel (256 images x 128 names sub-tiles)
+    g_sim_last_path = SCD_SIM_PATH_TILE;
     if (sm) {
         sim_topk_kernel<true, 8><<<g1, 512, 65536 + 32768, st>>>(f, wt, n, d, v, scale, cval, cidx, stats, 0);
         sim_refine_kernel<true, TOPM><<<g2, 256, 0, st>>>(f, wt, n, d, v, scale, k, cval, cidx, stats, hdr, fb, (long long*)idx_out, val_out, -1);

@@ -196,6 +196,14 @@ def sim_argmax(f, wsel_t, scale=100.0):
     return idx, val
 
 
+SIM_PATH_RB8, SIM_PATH_RC16, SIM_PATH_TILE, SIM_PATH_TILE768, SIM_PATH_SPLIT, SIM_PATH_REFINE4 = 1, 2, 4, 8, 16, 32     # include/scd_hip.h
+
+
+def sim_last_path():
+    """The kernels the last sim_topk / sim_argmax call of this process launched (scd_sim_last_path: a set of SIM_PATH_* bits)."""
+    return _L().scd_sim_last_path()
+
+
 def prompt_pool(emb, n_names, t_per, out, col0):
     """normalise -> mean -> normalise of each name's prompt embeddings into columns of out [d, V]."""
     _need_cuda(emb, out)
