@@ -131,14 +131,28 @@ extern "C" size_t scd_kmeans_estep_ws_bytes(int64_t n, int d, int k) {
 }
 
 // one block per (padded) centre: c' = (c-mu)*scale -> fp16; cn = ||c'||^2 (float64 -> float32)
+// cn doubles as the centre's state: a finite norm below 3.0e38 = live and inside the filters' range; +inf = dead (padding, NaN:
+// can never win); CN_WILD = live but OUTSIDE the range the filters' error bounds were derived for.  The bounds assume the centres lie
+// where the data lie (scale_kernel sets max |x'| in [8,16) from the ROWS); nothing makes a caller's centres do so, and two things break
+// far outside: a coordinate |c'_j| > 65,504 becomes an fp16 infinity (scores of -inf win with an infinite margin, or NaN keys), and on
+// the single-pass path ||c'||^2 / 8 leaves the fp16 range of the extension column - before that, already at ||c'||^2 / 2 + ||x'|| ||c'||
+// >= 240,000, a live centre's accumulator drops below the -4 * 60,000 a dead centre gets and a dead centre would take the label.
+// With ||x'|| <= 16 sqrt(Dp) = 362.04 at Dp = 512, ||c'||^2 <= 300 Dp = 153,600 gives 76,800 + 141,890 = 218,690 < 240,000; centres
+// inside the data box have ||c'||^2 < 256 Dp.  So: a live centre with a coordinate beyond fp16 is "wild" on every path, and one with
+// ||c'||^2 > 300 Dp where the extension column exists (Dp = 512, Kp <= 2048: estep_rb_kernel, and estep_rbm_kernel also at Kp = 128);
+// the streaming and legacy bounds scale with max ||c'|| and stay valid for long centres, which merely flag more rows there.  A
+// wild centre is dead to the filter (zero operand, never in a triple), and every decision stage that sees one sends EVERY row of the
+// call to the exact all-centres refine, which reads the float32 centres: slow, exact, and reachable only from outside the box.
+#define CN_WILD 3.2e38f
+__device__ __forceinline__ bool cn_is_wild(float v) { return v >= 3.0e38f && v < INFINITY; }
 // E-step operands of ONE centre (block-wide, 256 threads): norm, fp16 centred / scaled row (row-major and MFMA-fragment order),
 // fp32 transposed copy.  Called by prep_centers_kernel and, fused, by finalize_kernel (the block that has just produced the centre).
 __device__ __forceinline__ void prep_center_row(const float* C, int c, int k, int d, int dp, const PrepHdr* hdr,
                                                 const double* mu, EHdr* eh, float* cn, half_t* ch, float* ct, int kp,
                                                 int zero_counts, half_t* chf) {
     __shared__ double red[4];
-    __shared__ int bad;
-    if (threadIdx.x == 0) bad = 0;
+    __shared__ int bad, far;
+    if (threadIdx.x == 0) { bad = 0; far = 0; }
     if (zero_counts && c == 0 && threadIdx.x == 0) { eh->flag_cnt = 0; eh->full_cnt = 0; }   // streaming path: no memset launch
     __syncthreads();
     const double sc = (double)hdr->scale;
@@ -149,6 +163,7 @@ __device__ __forceinline__ void prep_center_row(const float* C, int c, int k, in
             float cv = C[(size_t)c * d + j];
             if (!isfinite(cv)) bad = 1;
             v = ((double)cv - mu[j]) * sc;
+            if (fabs(v) > 65504.0) far = 1;
         }
         ss += v * v;
         ch[(size_t)c * dp + j] = (half_t)(float)v;
@@ -163,16 +178,20 @@ __device__ __forceinline__ void prep_center_row(const float* C, int c, int k, in
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = ss;
     __syncthreads();
     const bool dead = (c >= k) || bad;
-    if (dead) {   // padded or NaN centre (empty cluster): can never win
+    const double t = red[0] + red[1] + red[2] + red[3];
+    const bool wild = !dead && (far || (dp == 512 && kp <= 2048 && t > 300.0 * dp));
+    if (dead || wild) {   // padded or NaN centre (empty cluster): can never win; wild centre: left to the exact refine
         for (int j = threadIdx.x; j < dp; j += 256) {
             ch[(size_t)c * dp + j] = (half_t)0.f;
             if (chf) chf[(((((size_t)(c >> 5) * (dp >> 7) + (j >> 7)) * 8 + ((j & 127) >> 4)) * 64 + (c & 31) + 32 * ((j >> 3) & 1)) << 3) + (j & 7)] = (half_t)0.f;
         }
     }
     if (threadIdx.x == 0) {
-        double t = red[0] + red[1] + red[2] + red[3];
         if (dead) {
             cn[c] = INFINITY;
+        } else if (wild) {
+            cn[c] = CN_WILD;
+            atomicMax(&eh->cmax_bits, 0x7f800000u);        // legacy path (the only reader of cmax_bits): an infinite bound
         } else {
             cn[c] = (float)t;
             atomicMax(&eh->cmax_bits, __float_as_uint((float)sqrt(t) * 1.0000002f));
@@ -321,10 +340,11 @@ __global__ void __launch_bounds__(256) estep_mfma_kernel(const half_t* __restric
         const float A = 1.5f * (2.02f * (9.765625e-4f + dp * 5.9604645e-8f) * cmax + 4.8e-7f * cmax + 6.0e-8f * sq);
         const float B = 1.5f * (6.0e-8f * sq * cmax + 2.4e-7f * cmax * cmax);
         const float E = A * xnorm[point] + B;
-        if (!(m1 - m0 > 2.0f * E)) {       // also catches NaN
+        const bool wild = !(cmax < INFINITY);   // a live centre outside the filter's range (prep_center_row): every row to all K
+        if (wild || !(m1 - m0 > 2.0f * E)) {       // also catches NaN
             // the true argmin is among the centres whose filtered score is within 2E of the best: if the third
             // smallest is already outside, only {j0, j1} need the exact distance; otherwise all K do.
-            const bool pair_only = (m2 - m0 > 2.0f * E) && j1 != 0x7fffffff;
+            const bool pair_only = !wild && (m2 - m0 > 2.0f * E) && j1 != 0x7fffffff;
             if (pair_only) {
                 const int pos = atomicAdd(&eh->flag_cnt, 1);
                 flag_list[pos] = (int)point;
@@ -854,12 +874,14 @@ __global__ void __launch_bounds__(256) estep_stream_kernel(const half_t* __restr
     __syncthreads();
 
     // decisions for all rows of the block
-    float cm2 = 0.f;
+    float cm2 = 0.f, wf = 0.f;
     for (int c = lane; c < kp_all; c += 64) {
         const float v = cn_all[c];
         if (v < 3.0e38f) cm2 = fmaxf(cm2, v);
+        if (cn_is_wild(v)) wf = 1.f;
     }
     cm2 = wave_max_f32(cm2);
+    const bool wild = wave_max_f32(wf) > 0.f;       // a live centre outside the filter's range (prep_center_row): every row to all K
     const float cmax = sqrtf(cm2) * 1.0000002f;
     const float sq = sqrtf((float)DP);
     // |s~ - s| <= A*||x'|| + B (see estep_mfma_kernel) + the key's low 7 bits: 2^-16 * (||c'||^2 + 2 ||x'|| ||c'||)
@@ -902,8 +924,8 @@ __global__ void __launch_bounds__(256) estep_stream_kernel(const half_t* __restr
         }
         labels[point] = j0;
         const float E = A * xn_r[j] + B;
-        if (!(m1 - m0 > 2.0f * E)) {       // also catches NaN
-            if (m2 - m0 > 2.0f * E) {
+        if (wild || !(m1 - m0 > 2.0f * E)) {       // also catches NaN
+            if (!wild && m2 - m0 > 2.0f * E) {
                 const int pos = atomicAdd(&cnts[0], 1);
                 l_flag[pos] = (int)point;
                 l_cand[pos] = j0 | (j1 << 16);
@@ -982,7 +1004,7 @@ __global__ void __launch_bounds__(256) estep_ext_kernel(const float* __restrict_
     *(half8*)(ext + (size_t)c * 8) = o;
 }
 // decision for one row from its three largest keys (shared by the kernel and by the merge of split row blocks)
-__device__ __forceinline__ void erb_decide(long long row, float b0, float b1, float b2, float cm2, const float* __restrict__ xnorm, EHdr* eh,
+__device__ __forceinline__ void erb_decide(long long row, float b0, float b1, float b2, float cm2, bool wild, const float* __restrict__ xnorm, EHdr* eh,
                                            int* flag_list, int* flag_cand, int* full_list, int32_t* __restrict__ labels) {
     constexpr int D = 512;
     // scores s = -2 * key value, ascending: m0 <= m1 <= m2
@@ -994,8 +1016,8 @@ __device__ __forceinline__ void erb_decide(long long row, float b0, float b1, fl
     const float B = 1.5f * (6.0e-8f * sq * cmax + 4.8e-7f * cmax * cmax + 2.45e-4f * cmax * cmax);
     labels[row] = j0;
     const float E = A * xnorm[row] + B;
-    if (!(m1 - m0 > 2.0f * E)) {                                 // also catches NaN
-        if (m2 - m0 > 2.0f * E) {
+    if (wild || !(m1 - m0 > 2.0f * E)) {                         // also catches NaN; wild: see prep_center_row
+        if (!wild && m2 - m0 > 2.0f * E) {
             const int pos = atomicAdd(&eh->flag_cnt, 1);
             flag_list[pos] = (int)row;
             flag_cand[pos] = j0 | (j1 << 16);
@@ -1160,12 +1182,14 @@ __global__ void __launch_bounds__(512) estep_rb_kernel(const half_t* __restrict_
         erb_insert(b0, b1, b2, o1);
         erb_insert(b0, b1, b2, o2);
     }
-    float cm2 = 0.f;
+    float cm2 = 0.f, wf = 0.f;
     for (int c = lane; c < kp_all; c += 64) {
         const float v = cn[c];
         if (v < 3.0e38f) cm2 = fmaxf(cm2, v);
+        if (cn_is_wild(v)) wf = 1.f;
     }
     cm2 = wave_max_f32(cm2);
+    const bool wild = wave_max_f32(wf) > 0.f;
     if (hh != 0 || row >= n) return;
     if (split) {                                                 // this part's three best of the row, for estep_rb_merge_kernel
         const long long trows = n - (long long)nfull * 256, tr = row - (long long)nfull * 256;
@@ -1174,7 +1198,7 @@ __global__ void __launch_bounds__(512) estep_rb_kernel(const half_t* __restrict_
         tkeys[((size_t)part * 3 + 2) * trows + tr] = b2;
         return;
     }
-    erb_decide(row, b0, b1, b2, cm2, xnorm, eh, flag_list, flag_cand, full_list, labels);
+    erb_decide(row, b0, b1, b2, cm2, wild, xnorm, eh, flag_list, flag_cand, full_list, labels);
 #undef ERB_RD
 #undef ERB_RDX
 #undef ERB_WAIT
@@ -1235,13 +1259,15 @@ __global__ void __launch_bounds__(512) estep_rbm_kernel(const half_t* __restrict
     }
     for (int sg = wave; sg < nseg; sg += 8) {
         const float* cn = (const float*)(a.ws0 + (size_t)slot_of(sg) * a.ws_stride + a.cn_off);
-        float cm2 = 0.f;
+        float cm2 = 0.f, wf = 0.f;
         for (int c = lane; c < kp; c += 64) {
             const float v = cn[c];
             if (v < 3.0e38f) cm2 = fmaxf(cm2, v);
+            if (cn_is_wild(v)) wf = 1.f;
         }
         cm2 = wave_max_f32(cm2);
-        if (lane == 0) cm2s[sg] = cm2;
+        wf = wave_max_f32(wf);
+        if (lane == 0) cm2s[sg] = wf > 0.f ? -1.f : cm2;           // negative: the segment has a wild centre (prep_center_row)
     }
 
     half8 bf[32];
@@ -1302,13 +1328,15 @@ __global__ void __launch_bounds__(512) estep_rbm_kernel(const half_t* __restrict
         // (a segment holds at most 256 centres: EIGHT index bits in a key, i.e. a relative perturbation below 2^-15 of the score where
         // estep_rb_kernel's eleven bits cost 2^-12 - the key terms of the bound shrink by 8 and with them the rows sent to the refine)
         const unsigned j0 = __float_as_uint(b0) & 255u, j1 = __float_as_uint(b1) & 255u;
-        const float cmax = sqrtf(cm2s[sg]) * 1.0000002f;
+        const bool wild = cm2s[sg] < 0.f;
+        const float cmax = sqrtf(fmaxf(cm2s[sg], 0.f)) * 1.0000002f;
         const float sq = 22.627417f;                             // sqrt(512)
         const float A = 1.5f * (2.02f * (9.765625e-4f + D * 5.9604645e-8f) * cmax + 4.8e-7f * cmax + 6.0e-8f * sq + 6.2e-5f * cmax);
         const float B = 1.5f * (6.0e-8f * sq * cmax + 4.8e-7f * cmax * cmax + 3.1e-5f * cmax * cmax);
         const float E = A * xn + B;
         unsigned state = 0u;
         if (!(m1 - m0 > 2.0f * E)) state = (m2 - m0 > 2.0f * E) ? 1u : 2u;     // also catches NaN
+        if (wild) state = 2u;
         const unsigned packed = j0 | (j1 << 8) | (state << 16);
 #pragma unroll
         for (int i = 0; i < MAXSEG; ++i) resv[i] = (i == sg) ? packed : resv[i];
@@ -1432,19 +1460,21 @@ __global__ void __launch_bounds__(256) estep_rb_merge_kernel(const float* __rest
                                                              const float* __restrict__ xnorm, const float* __restrict__ cn, int kp,
                                                              EHdr* eh, int* flag_list, int* flag_cand, int* full_list,
                                                              int32_t* __restrict__ labels) {
-    float cm2 = 0.f;
+    float cm2 = 0.f, wf = 0.f;
     for (int c = threadIdx.x & 63; c < kp; c += 64) {
         const float v = cn[c];
         if (v < 3.0e38f) cm2 = fmaxf(cm2, v);
+        if (cn_is_wild(v)) wf = 1.f;
     }
     cm2 = wave_max_f32(cm2);
+    const bool wild = wave_max_f32(wf) > 0.f;
     const long long trows = n - row0, tr = (long long)blockIdx.x * 256 + threadIdx.x;
     if (tr >= trows) return;
     float b0 = -INFINITY, b1 = -INFINITY, b2 = -INFINITY;
     for (int p = 0; p < nsplit; ++p)
 #pragma unroll
         for (int q = 0; q < 3; ++q) erb_insert(b0, b1, b2, tkeys[((size_t)p * 3 + q) * trows + tr]);
-    erb_decide(row0 + tr, b0, b1, b2, cm2, xnorm, eh, flag_list, flag_cand, full_list, labels);
+    erb_decide(row0 + tr, b0, b1, b2, cm2, wild, xnorm, eh, flag_list, flag_cand, full_list, labels);
 }
 
 // exact re-evaluation of flagged rows: one wave per row, float64 difference form over all K centres
