@@ -1906,8 +1906,15 @@ extern "C" int scd_kmeans_dist(scd_handle h, const float* X, const float* C, int
 // (M-step partial sums: see mstep.hip)
 
 // double-double helpers (used by finalize_kernel's fused inertia and the incremental M-step further down)
+// No floating-point contraction inside them: the error-free transformations need every product and sum rounded exactly as written.
+// With contraction on (the compiler's default for device code, and this target fuses a product into EVERY sum that uses it), in
+// dd_add_prod's `a.hi + p` and `p - bb` the rounded product p became the exact x * y while its rounding error fma(x, y, -p) was still
+// added: counted twice, the result was a plain double's (2^-53 of the largest products, not 2^-100).  The pragma is honoured under
+// the compiler's default -ffp-contract=fast-honor-pragmas only: this file must not be built with -ffp-contract=fast or fast-math
+// (tests/test_gpu_mstep.py's k = 7 script fails if it is).
 struct dd_t { double hi, lo; };
 __device__ __forceinline__ dd_t dd_add_d(dd_t a, double b) {      // a + b, b a plain double
+#pragma clang fp contract(off)
     const double s = a.hi + b;
     const double bb = s - a.hi;
     const double e = (a.hi - (s - bb)) + (b - bb);
@@ -1917,6 +1924,7 @@ __device__ __forceinline__ dd_t dd_add_d(dd_t a, double b) {      // a + b, b a 
 }
 __device__ __forceinline__ dd_t dd_add(dd_t a, dd_t b) { return dd_add_d(dd_add_d(a, b.hi), b.lo); }
 __device__ __forceinline__ dd_t dd_add_prod(dd_t a, double x, double y) {    // a + x * y, the product error-free
+#pragma clang fp contract(off)
     const double p = x * y;
     const double e = fma(x, y, -p);
     return dd_add_d(dd_add_d(a, p), e);
