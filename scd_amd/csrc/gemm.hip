@@ -454,6 +454,7 @@ __global__ void __launch_bounds__(BM * 2, 2) gemm_dma_kernel(const half_t* __res
 typedef float f32x4v __attribute__((ext_vector_type(4)));
 typedef float float2v __attribute__((ext_vector_type(2)));
 typedef _Float16 half2v __attribute__((ext_vector_type(2)));
+typedef unsigned u32x4v __attribute__((ext_vector_type(4)));
 
 // ------------------------------------------------------------------------------------------------
 // Four-wave kernel: 256x256 block tile, one wave per SIMD, each wave a 128(m) x 128(n) sub-tile whose 256 accumulator
@@ -635,7 +636,7 @@ gemm_w4_kernel(const half_t* __restrict__ A, const half_t* __restrict__ W, const
     };
     tile_ptrs();
     auto issue_advance = [&]() {
-        if (++nkt == nkc) {
+        if (__builtin_expect(++nkt == nkc, 0)) {
             nkt = 0;
             if (++ntiles < my_tiles) { it_step(nit); tile_ptrs(); }
         }
@@ -679,12 +680,15 @@ gemm_w4_kernel(const half_t* __restrict__ A, const half_t* __restrict__ W, const
     }                                                                                                            \
     __builtin_amdgcn_s_setprio(0);
 #define W4_H_NONE(i)
-    // even sub-step: reads the odd sub-step's fragments (k-half 1 of the same slot) under MFMAs 0..47 and issues the W part
-    // of the refill that the previous odd sub-step began (the other slot), one fill per four MFMAs of the first half
+    // even sub-step: reads the odd sub-step's fragments (k-half 1 of the same slot) under MFMAs 24..47 and issues the W part
+    // of the refill that the previous odd sub-step began (the other slot), one fill per four MFMAs of the first half.
+    // (Until 2026-10 the reads ran under MFMAs 0..47 with the index taken mod 8, so every fragment was read twice and the first
+    // copy - sixteen ds_read_b128 per chunk and wave, a third of the kernel's LDS read traffic - was overwritten unread.  The
+    // surviving copy keeps its place in the stream.)
 #define W4_H_EVEN(i)                                                                                             \
     if ((i) < 32 && ((i) & 3) == 2) issue_w(((i) >> 2) & 7, cslot ^ 1);                                          \
-    if ((i) < 48 && (i) % 3 == 0) W4_RD(fwB[((i) / 3) & 7], fw1 + so, (((i) / 3) & 7) * 2048);                   \
-    if ((i) < 48 && (i) % 3 == 1) W4_RD(faB[((i) / 3) & 7], fa1 + so, (((i) / 3) & 7) * 2048);
+    if ((i) >= 24 && (i) < 48 && (i) % 3 == 0) W4_RD(fwB[((i) / 3) & 7], fw1 + so, (((i) / 3) & 7) * 2048);      \
+    if ((i) >= 24 && (i) < 48 && (i) % 3 == 1) W4_RD(faB[((i) / 3) & 7], fa1 + so, (((i) / 3) & 7) * 2048);
     // odd sub-step: the chunk's barrier sits after MFMA L0-1, so everything that needs it hangs under MFMAs L0..63: the next
     // chunk's first fragments (other slot; W under L0, L0+2, .., A under L0+16, ..) and the A part - the one that can miss L2 - of
     // the refill of this slot with chunk c+2, one fill per LS MFMAs.  Measured: a wave is held ~64 cycles per fill while the CU's
@@ -711,13 +715,13 @@ gemm_w4_kernel(const half_t* __restrict__ A, const half_t* __restrict__ W, const
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                                                         \
         __builtin_amdgcn_s_barrier();                                                                            \
         asm volatile("" ::: "memory");                                                                           \
-        /* past this block's last chunk the refill re-reads the current tile's first chunk into the free slot: no branch  \
-           around the asm groups (a diamond makes hipcc copy accumulators between paths), and nothing reads the slot */   \
-        if (g + 2 < chunks) {                                                                                    \
-            ga = ga_t + (IMG ? img_chunk(nkt) : nkt * 64);                                                       \
-            gw = gw_t + nkt * 64;                                                                                \
-            if constexpr (IMG) { if (nkt == 0) img_offsets(nit.bm); }                                            \
-        } else chunk_ptrs(cit, 0);                                                                               \
+        /* past this block's last chunk the refill goes on: nkt wraps to 0 and the panel bases stay those of the block's   \
+           last tile (issue_advance), so the two tail refills re-read that tile's chunks 0 and 1 into slots nothing reads  \
+           any more.  No branch around the asm groups (a diamond makes hipcc copy accumulators between paths) and no       \
+           select either: s_cmp + four s_cselect + the other pointer pair, paid in every chunk for two chunks per block */ \
+        ga = ga_t + (IMG ? img_chunk(nkt) : nkt * 64);                                                           \
+        gw = gw_t + nkt * 64;                                                                                    \
+        if constexpr (IMG) { if (nkt == 0) img_offsets(nit.bm); }                                                \
         issue_advance();                                                                                         \
         W4_SUB_RANGE(fwB, faB, 0, W4_H_ODD, LATE_TM, 8)                                                          \
         cslot ^= 1;                                                                                              \
@@ -735,7 +739,7 @@ gemm_w4_kernel(const half_t* __restrict__ A, const half_t* __restrict__ W, const
         f32x4v acc[8][8];   // [tn][tm]; first written by the C = 0 MFMAs of the first sub-step
         f32x4v bq[8], sq[8];
         float2 lrs[8];
-        float keep1[2] = {0.f, 0.f}, keep2[2] = {0.f, 0.f};   // LN = 2: this lane's rows 4*c16 + 64*j + q16
+        float keep1[2] = {0.f, 0.f}, keep2[2] = {0.f, 0.f};   // LN = 2: this lane's rows 4*(15 - c16) + 64*j + q16
         // bias and the first residual rows are fetched one chunk before the tile ends: a plain load issued in the epilogue
         // would sit behind the ring refills in the (in-order) vmcnt queue and stall on them.
 #define W4_PRE()                                                                                                 \
@@ -763,7 +767,7 @@ gemm_w4_kernel(const half_t* __restrict__ A, const half_t* __restrict__ W, const
         W4_EVEN(1)
         W4_ODD()
         for (int kc = 1; kc < nkc; ++kc) {
-            if (kc == nkc - 1) W4_PRE()
+            if (__builtin_expect(kc == nkc - 1, 0)) W4_PRE()
             W4_EVEN(0)
             W4_ODD()
         }
@@ -778,7 +782,7 @@ gemm_w4_kernel(const half_t* __restrict__ A, const half_t* __restrict__ W, const
         // software pipeline over the 8 m-tiles: the patch read of m-tile tm-1 is in flight while m-tile tm is converted,
         // and its rows are stored after that (one wave per SIMD: nothing else would cover the LDS round trip)
         half8 hvb[4];
-        unsigned stash[8][16];
+        u32x4v stash[8][4];
         float rstd_a[8], nmr_a[8];
         if (LN == 1) {
             // {rstd, -mean * rstd} of the row, formed once per row by ln_finish_kernel from the fixed-point row sums (as eight
@@ -853,10 +857,16 @@ gemm_w4_kernel(const half_t* __restrict__ A, const half_t* __restrict__ W, const
                         W4_DPP_ADD(s1, 0x4E); W4_DPP_ADD(s2, 0x4E);     // quad_perm [2,3,0,1]
                         W4_DPP_ADD(s1, 0xB1); W4_DPP_ADD(s2, 0xB1);     // quad_perm [1,0,3,2]
 #undef W4_DPP_ADD
-                        // every lane of the row group now holds the totals; lane c16 keeps those of (tm*4+p) == c16 (mod 16)
-                        const bool mine = ((ts * 4 + p) & 15) == c16;
-                        keep1[ts >> 2] = mine ? s1 : keep1[ts >> 2];
-                        keep2[ts >> 2] = mine ? s2 : keep2[ts >> 2];
+                        // every lane of the row group now holds the totals.  keep is a shift register along the 16 lanes (c16)
+                        // of that group: row_shr:1 moves what was kept one lane up and lane 0, which has no source lane, takes the
+                        // new totals (update_dpp's "old" operand, bound_ctrl off).  After the 16 row groups k = (ts & 3) * 4 + p of a
+                        // 64-row half, lane c16 holds those of k = 15 - c16.  One v_mov_dpp per value like the select it replaces
+                        // (k == c16 ? s : keep), whose sixteen lane masks held 32 SGPRs through the kernel: with them the variant
+                        // spilled 39 SGPRs to lanes and read nine of them back inside the chunk loop
+#define W4_KEEP(K, V) K = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, V), __builtin_bit_cast(int, K), 0x111, 0xF, 0xF, false))
+                        W4_KEEP(keep1[ts >> 2], s1);   // row_shr:1
+                        W4_KEEP(keep2[ts >> 2], s2);
+#undef W4_KEEP
                     }
                     // a large C streams past L2 ("nt"): written normally, each round of tiles pushes 32 MB of dirty lines
                     // through the 32 MB of L2 and evicts the W panels every CU is about to re-read (measured +12 % on the
@@ -866,11 +876,11 @@ gemm_w4_kernel(const half_t* __restrict__ A, const half_t* __restrict__ W, const
                         // queue until those have drained (measured: 17 k cycles of epilogue against 6 k without the stores).
                         // The finished rows are parked in the accumulator registers their m-tile has just vacated and all
                         // 32 stores are issued after the last residual load.
-                        const uint4 w4 = __builtin_bit_cast(uint4, hv);
-                        asm volatile("v_accvgpr_write_b32 %0, %1" : "=a"(stash[ts][p * 4 + 0]) : "v"(w4.x));
-                        asm volatile("v_accvgpr_write_b32 %0, %1" : "=a"(stash[ts][p * 4 + 1]) : "v"(w4.y));
-                        asm volatile("v_accvgpr_write_b32 %0, %1" : "=a"(stash[ts][p * 4 + 2]) : "v"(w4.z));
-                        asm volatile("v_accvgpr_write_b32 %0, %1" : "=a"(stash[ts][p * 4 + 3]) : "v"(w4.w));
+                        // The row is parked as ONE 128-bit value of register class "a" (the copy is hipcc's: four
+                        // v_accvgpr_write, hazards padded by the compiler), so it sits in four consecutive, 64-bit-aligned
+                        // accumulator registers and the store below can name them as its data operand.
+                        const u32x4v w4 = __builtin_bit_cast(u32x4v, hv);
+                        asm volatile("" : "=a"(stash[ts][p]) : "0"(w4));
                     } else if (NTS) {
                         // (s_nop 1 behind every asm store: a VMEM store of more than 64 bits must not be followed within two wait
                         // states by a write of its data registers, and hipcc's hazard recognizer cannot see a store inside inline asm -
@@ -894,26 +904,35 @@ gemm_w4_kernel(const half_t* __restrict__ A, const half_t* __restrict__ W, const
             }
         }
         if (DEFER_ST) {
+            // The stores read their data from the parked accumulator registers (a VMEM data operand may be an AGPR on gfx90a and
+            // later): no v_accvgpr_read back into VGPRs, 128 per tile.  Hazards, by the ISA's rules for a store of more than 64 bits:
+            // its data registers must not be WRITTEN within two wait states behind it.  Inside a statement of four stores nothing
+            // writes a register; behind it the s_nop 1 covers whatever hipcc places next (it cannot see the stores).  The writers
+            // that matter are the next tile's C = 0 MFMAs, which reuse these registers as accumulators: they come behind the
+            // last statement's s_nop 1 and at least the s_waitcnt / s_setprio pair that opens the even sub-step.  That the
+            // stores have READ the registers by then needs no vmcnt wait: a store reads its data when it issues, in order, and
+            // only its completion in memory is counted.  The parked values are last written by hipcc's own v_accvgpr_write
+            // copies long before (VALU write -> VMEM read of a VGPR is interlocked).
 #pragma unroll
-            for (int ts = 0; ts < 8; ++ts)
-#pragma unroll
-                for (int p = 0; p < 4; ++p) {
-                    uint4 w4;
-                    asm volatile("v_accvgpr_read_b32 %0, %1" : "=v"(w4.x) : "a"(stash[ts][p * 4 + 0]));
-                    asm volatile("v_accvgpr_read_b32 %0, %1" : "=v"(w4.y) : "a"(stash[ts][p * 4 + 1]));
-                    asm volatile("v_accvgpr_read_b32 %0, %1" : "=v"(w4.z) : "a"(stash[ts][p * 4 + 2]));
-                    asm volatile("v_accvgpr_read_b32 %0, %1" : "=v"(w4.w) : "a"(stash[ts][p * 4 + 3]));
-                    const half8 hv = __builtin_bit_cast(half8, w4);
-                    half_t* const crow = Ct + (size_t)((ts * 16 + p * 4) * N);
-                    if (NTS) asm volatile("global_store_dwordx4 %0, %1, %2 nt\n\ts_nop 1" ::"v"(lane_el * 2u), "v"(hv), "s"(crow) : "memory");
-                    else *(half8*)(crow + lane_el) = hv;
-                }
+            for (int ts = 0; ts < 8; ++ts) {
+                half_t* const c0 = Ct + (size_t)((ts * 16 + 0) * N);
+                half_t* const c1 = Ct + (size_t)((ts * 16 + 4) * N);
+                half_t* const c2 = Ct + (size_t)((ts * 16 + 8) * N);
+                half_t* const c3 = Ct + (size_t)((ts * 16 + 12) * N);
+#define W4_ST4(NT)                                                                                               \
+    asm volatile("global_store_dwordx4 %0, %1, %5" NT "\n\tglobal_store_dwordx4 %0, %2, %6" NT "\n\t"                 \
+                 "global_store_dwordx4 %0, %3, %7" NT "\n\tglobal_store_dwordx4 %0, %4, %8" NT "\n\ts_nop 1"          \
+                 ::"v"(lane_el * 2u), "a"(stash[ts][0]), "a"(stash[ts][1]), "a"(stash[ts][2]), "a"(stash[ts][3]),    \
+                   "s"(c0), "s"(c1), "s"(c2), "s"(c3) : "memory")
+                if (NTS) W4_ST4(" nt"); else W4_ST4("");
+#undef W4_ST4
+            }
         }
         if (LN == 2) {
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
                 // fixed point so that the six partial sums of a row (3 tile columns x 2 waves) add up deterministically
-                unsigned long long* dst = (unsigned long long*)(ln_out + 2 * ((size_t)bm * BM + wm * 128)) + (unsigned)(2 * (4 * c16 + 64 * j + q16));
+                unsigned long long* dst = (unsigned long long*)(ln_out + 2 * ((size_t)bm * BM + wm * 128)) + (unsigned)(2 * (4 * (15 - c16) + 64 * j + q16));
                 atomicAdd(dst, (unsigned long long)__float2ll_rn(keep1[j] * 16777216.f));
                 atomicAdd(dst + 1, (unsigned long long)__float2ll_rn(keep2[j] * 1048576.f));
             }
