@@ -352,6 +352,32 @@ int scd_vote_table(scd_handle h, const int64_t* name_idx, int64_t n, int ld, int
 int scd_vote_table_topm(scd_handle h, int32_t* counts, const int64_t* first, int n_clusters, int64_t v, int m, int64_t* keys_out,
                         int32_t* counts_out, void* stream);
 
+/* ---- clustering scores: the contingency table of a clustering against targets and the statistics ACC / NMI / ARI / purity are
+ * computed from.  scd_contingency replaces the counting loop of cluster_acc (gcd/project_utils/cluster_utils.py:39-62:
+ * `w[y_pred[i], y_true[i]] += 1`) and the `contingency_matrix` sklearn builds inside nmi_score / ari_score / purity_score
+ * (cluster_utils.py:65-69); with `subset` it builds the tables of the labelled and of the unlabelled rows, which one evaluation of
+ * GCD's estimator scores separately (gcd/methods/estimate_k/estimate_k.py:87-94: `[mask]` / `[~mask]`), in one pass.
+ * pred, truth int32 [n]; subset uint8 [n] or NULL; table_out int32 [S, kp, kt] with S = 1 (subset NULL) or 2: row i adds one to
+ * table (subset[i] != 0 ? 0 : 1), cell (pred[i], truth[i]).  A row with pred outside [0, kp) or truth outside [0, kt) is counted in
+ * n_bad_out (int64 [1]) and in no table.  Both outputs are zeroed by the call.  Integer counts: exact, whatever the arrival order.
+ * Two kernels: up to scd_contingency_private_cells() cells (S * kp * kt; the table as uint32 in one block's LDS) every block counts a
+ * contiguous row range in LDS and adds its non-zero cells to the table; above that, one global integer add per row.
+ * scd_contingency_last_path: which of them the handle's last scd_contingency launched (-1 before the first call). */
+enum { SCD_CONTINGENCY_PRIVATE = 0, SCD_CONTINGENCY_GLOBAL = 1 };
+size_t scd_contingency_private_cells(void);
+int scd_contingency(scd_handle h, const int32_t* pred, const int32_t* truth, const uint8_t* subset, int64_t n, int kp, int kt,
+                    int32_t* table_out, int64_t* n_bad_out, void* stream);
+int scd_contingency_last_path(scd_handle h);
+/* The statistics of S tables int32 [S, kp, kt] (non-negative cells, fewer than 2^31 rows per table), a kernel of its own so that
+ * ranks can add their tables first.  ints_out int64 [S, 6]: n, sum n_ij^2, sum a_i^2 (a: row sums, the predictions), sum b_j^2
+ * (b: column sums, the targets), sum_i max_j n_ij (the purity numerator, cluster_utils.py:65-69), the number of non-zero cells - all
+ * exact.  info_out float64 [S, 3]: H(pred), H(truth) and the mutual information in nats, term by term as sklearn's `entropy` and
+ * `mutual_info_score` form them (terms below 2^-52 in magnitude count as 0), summed over a fixed strided partition and a fixed tree:
+ * bit-identical from call to call.  An empty table gives zeros. */
+size_t scd_contingency_stats_ws_bytes(int s, int kp, int kt);
+int scd_contingency_stats(scd_handle h, const int32_t* table, int s, int kp, int kt, int64_t* ints_out, double* info_out, void* ws,
+                          size_t ws_bytes, void* stream);
+
 /* ---- host solvers (CPU, synchronous) ---- */
 /* linear_assignment (gcd/project_utils/cluster_utils.py:234-493), same tie-breaking; pairs_out [min(n,m),2] sorted */
 int scd_munkres(const int64_t* cost, int n, int m, int64_t* pairs_out, int* n_pairs_out);

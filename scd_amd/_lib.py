@@ -120,6 +120,13 @@ SIGNATURES = {
     "scd_vote_hist": (_i, [_vp, _vp, _i64, _i, _i, _vp, _vp, _i, _vp, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     "scd_vote_table": (_i, [_vp, _vp, _i64, _i, _i, _vp, _vp, _i, _i64, _i64, _i, _vp, _vp, _vp]),
     "scd_vote_table_topm": (_i, [_vp, _vp, _vp, _i, _i64, _i, _vp, _vp, _vp]),
+    "scd_contingency_private_cells": (_sz, []),
+    # h, pred, truth, subset, n, kp, kt, table_out, n_bad_out, stream
+    "scd_contingency": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _vp, _vp, _vp]),
+    "scd_contingency_last_path": (_i, [_vp]),
+    "scd_contingency_stats_ws_bytes": (_sz, [_i, _i, _i]),
+    # h, table, s, kp, kt, ints_out, info_out, ws, ws_bytes, stream
+    "scd_contingency_stats": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     "scd_munkres": (_i, [_vp, _i, _i, _vp, C.POINTER(_i)]),
     "scd_munkres_sparse": (_i, [_i, _i64, _vp, _vp, _vp, _vp, C.POINTER(_i)]),
     "scd_transport_solve": (_i, [_vp, _i64, _i, _i, _i, _vp, C.POINTER(_i64)]),

@@ -196,6 +196,7 @@ class KMeans:
                 better = inertia < best[1] and not _same_clustering(labels, best[0], self.n_clusters)
             if better:
                 best = (labels, inertia, centers, n_iter)
+        self.labels_device_ = best[0]             # the best start's labels, int32 on the device: scd_amd.metrics scores them in place
         self.labels_ = best[0].cpu().numpy().astype(np.int32)
         self.inertia_ = best[1]
         self.cluster_centers_ = best[2].cpu().numpy()

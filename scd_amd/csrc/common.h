@@ -32,6 +32,7 @@ struct scd_ctx {
     double* run_host = nullptr;
     double* run_dev = nullptr;
     double run_seq = 0.0;
+    int cont_path = -1;     // scd_contingency_last_path: SCD_CONTINGENCY_PRIVATE / _GLOBAL of the last scd_contingency, -1 before the first
 };
 #define SCD_SCRATCH_BYTES (262144 + 64)
 

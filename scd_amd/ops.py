@@ -818,6 +818,51 @@ def vote_table_topm(counts, first, m):
     return keys, cnt
 
 
+# ----------------------------------------------------------------------------- clustering scores
+def contingency_private_cells():
+    """The largest S * kp * kt for which scd_contingency counts in per-block LDS tables (above it: one global add per row)."""
+    return int(_L().scd_contingency_private_cells())
+
+
+def contingency(pred, truth, subset, kp, kt):
+    """scd_contingency: pred, truth int32 [n] and subset uint8 [n] or None on the device -> (table int32 [S, kp, kt], n_bad int64 [1]),
+    S = 1 without subset, else 2 (table 0: rows with subset != 0).  Rows with a label outside the table are counted in n_bad only."""
+    _need_cuda(pred, truth, subset)
+    if pred.dtype != torch.int32 or truth.dtype != torch.int32 or (subset is not None and subset.dtype != torch.uint8):
+        raise _lib.ScdError(_lib.SCD_EINVAL, "contingency: pred / truth must be int32 and subset uint8")
+    pred, truth = pred.contiguous(), truth.contiguous()
+    subset = None if subset is None else subset.contiguous()
+    n = pred.numel()
+    if truth.numel() != n or (subset is not None and subset.numel() != n):
+        raise _lib.ScdError(_lib.SCD_EINVAL, "contingency: pred, truth and subset must have one length")
+    s = 1 if subset is None else 2
+    table = torch.empty((s, int(kp), int(kt)), dtype=torch.int32, device=pred.device)
+    n_bad = torch.empty(1, dtype=torch.int64, device=pred.device)
+    check(_L().scd_contingency(handle(), ptr(pred), ptr(truth), ptr(subset), n, int(kp), int(kt), ptr(table), ptr(n_bad), stream_ptr()))
+    return table, n_bad
+
+
+def contingency_last_path():
+    """0: the last contingency() counted in per-block LDS tables, 1: with one global add per row (-1 before the first call)."""
+    return int(_L().scd_contingency_last_path(handle()))
+
+
+def contingency_stats(table):
+    """scd_contingency_stats of table int32 [S, kp, kt]: (ints int64 [S, 6] = n, sum n_ij^2, sum a_i^2, sum b_j^2, sum_i max_j n_ij,
+    non-zero cells; info float64 [S, 3] = H(pred), H(truth), MI in nats) on the device."""
+    _need_cuda(table)
+    if table.dtype != torch.int32 or table.dim() != 3:
+        raise _lib.ScdError(_lib.SCD_EINVAL, "contingency_stats: table must be int32 [S, kp, kt]")
+    table = table.contiguous()
+    s, kp, kt = table.shape
+    ints = torch.empty((s, 6), dtype=torch.int64, device=table.device)
+    info = torch.empty((s, 3), dtype=torch.float64, device=table.device)
+    nb = _L().scd_contingency_stats_ws_bytes(s, kp, kt)
+    ws = _ws(nb, table.device)
+    check(_L().scd_contingency_stats(handle(), ptr(table), s, kp, kt, ptr(ints), ptr(info), ptr(ws), nb, stream_ptr()))
+    return ints, info
+
+
 # ----------------------------------------------------------------------------- host solvers
 def munkres(cost):
     """linear_assignment (cluster_utils.py:234): int array [n,m] -> sorted pairs [min(n,m),2]."""
