@@ -4,12 +4,18 @@ to for an unknown class number) on the feature caches main_unsup.py / main_ptsup
   ROOT/extracted_features/{feat_model}_{dataset_name}_all.pt     dict all_feats, mask_lab, targets (main_unsup.py:141-146)
 
 All features, labelled and unlabelled, are L2-normalised once (estimate_k.py:61) and clustered with
-`KMeans(n_clusters=K, random_state=0)` for the Ks a bounded Brent search (default, :221-242) or the reference's binary search
-(:172-218) asks for; the K with the highest clustering accuracy on the labelled rows wins.  Fits and scores run on the GPU
-(scd_amd.cluster.KMeans, scd_amd.metrics).  Writes ROOT/cluster/estimated_k_{feat_model}_{dataset_name}.json and prints the value to
-pass as --n_cluster.
+`KMeans(n_clusters=K, random_state=0)` for the Ks a search asks for.  Two criteria:
 
-  python estimate_k.py --root_dir ROOT --dataset_name cub --feat_model clip [--max_classes 1000] [--search_mode brent|binary]
+  --criterion acc (default)   GCD's: the K with the highest clustering accuracy on the LABELLED rows wins; bounded Brent search
+                              (default, :221-242) or the reference's binary search (:172-218).  Needs labelled rows.
+  --criterion silhouette      label-free: the K with the highest mean silhouette coefficient over all rows wins; integer grid search
+                              by default.  For caches without labelled rows (main_unsup.py's setting).
+
+Fits and scores run on the GPU (scd_amd.cluster.KMeans, scd_amd.metrics).  Writes
+ROOT/cluster/estimated_k_{feat_model}_{dataset_name}.json and prints the value to pass as --n_cluster.
+
+  python estimate_k.py --root_dir ROOT --dataset_name cub --feat_model clip [--max_classes 1000] [--search_mode brent|binary|grid]
+  python estimate_k.py --root_dir ROOT --dataset_name D --feat_model clip --criterion silhouette --max_classes 1000
 """
 import argparse
 import json
@@ -29,44 +35,74 @@ def build_parser():
     p.add_argument('--feat_model', type=str, default='clip', help='{feat_model} of the cache file name')
     p.add_argument('--max_classes', default=1000, type=int)
     p.add_argument('--min_classes', default=None, type=int,
-                   help='default: the number of distinct targets among the labelled rows (the reference\'s num_labeled_classes)')
-    p.add_argument('--search_mode', type=str, default='brent', choices=['brent', 'binary'], help='Mode for black box optimisation')
+                   help='default: acc - the number of distinct targets among the labelled rows (the reference\'s num_labeled_classes); '
+                        'silhouette - 2')
+    p.add_argument('--criterion', type=str, default='acc', choices=['acc', 'silhouette'],
+                   help='acc: clustering accuracy on the labelled rows (GCD); silhouette: mean silhouette coefficient, needs no labels')
+    p.add_argument('--search_mode', type=str, default=None, choices=['brent', 'binary', 'grid'],
+                   help='Mode for black box optimisation; default: brent for acc, grid for silhouette')
     return p
 
 
-def main(argv=None):
+def parse_args(argv=None):
+    """The parsed arguments with the criterion-dependent defaults resolved."""
     args = build_parser().parse_args(argv)
+    if args.search_mode is None:
+        args.search_mode = 'brent' if args.criterion == 'acc' else 'grid'
+    if args.min_classes is None and args.criterion == 'silhouette':
+        args.min_classes = 2
+    return args
+
+
+def main(argv=None):
+    args = parse_args(argv)
     assert torch.cuda.is_available(), "estimate_k.py needs a HIP device"
     dev = torch.device("cuda")
     path = os.path.join(args.root_dir, 'extracted_features', f'{args.feat_model}_{args.dataset_name}_all.pt')
     data = torch.load(path, weights_only=False)
     mask_lab = np.asarray(data['mask_lab']).astype(bool)
     targets = np.asarray(data['targets']).astype(int)
-    if not mask_lab.any():
+    sil = args.criterion == 'silhouette'
+    if not sil and not mask_lab.any():
         raise SystemExit("the cache has no labelled row: the estimator scores K on the labelled rows")
     feats = ops.l2norm_rows(torch.as_tensor(np.asarray(data['all_feats'])).to(dev).float())
-    small_k = args.min_classes if args.min_classes is not None else len(np.unique(targets[mask_lab]))
-    big_k = min(args.max_classes, feats.shape[0])
+    if sil:
+        small_k = args.min_classes
+        big_k = min(args.max_classes, feats.shape[0] - 1)       # the silhouette needs fewer clusters than rows
+    else:
+        small_k = args.min_classes if args.min_classes is not None else len(np.unique(targets[mask_lab]))
+        big_k = min(args.max_classes, feats.shape[0])
     if big_k <= small_k:
         raise SystemExit(f"--max_classes {big_k} must be above the smallest K searched, {small_k}")
-    print(f'{feats.shape[0]} rows, {int(mask_lab.sum())} labelled; searching K in [{small_k}, {big_k}] ({args.search_mode})')
-    targets_dev = torch.as_tensor(targets, device=dev)
-    mask_dev = torch.as_tensor(mask_lab, device=dev)
+    print(f'{feats.shape[0]} rows, {int(mask_lab.sum())} labelled; searching K in [{small_k}, {big_k}] ({args.search_mode}, {args.criterion})')
     scores = {}
 
-    def evaluate(K):
-        acc, scores[int(K)] = ek.evaluate_k(K, feats, targets_dev, mask_dev, verbose=True)
-        return acc
+    if sil:
+        def evaluate(K):
+            s, scores[int(K)] = ek.evaluate_k_unlabelled(K, feats, verbose=True)
+            return s
+        name = 'silhouette'
+    else:
+        targets_dev = torch.as_tensor(targets, device=dev)
+        mask_dev = torch.as_tensor(mask_lab, device=dev)
+
+        def evaluate(K):
+            acc, scores[int(K)] = ek.evaluate_k(K, feats, targets_dev, mask_dev, verbose=True)
+            return acc
+        name = 'labelled_acc'
 
     if args.search_mode == 'brent':
         print('Optimising with Brents algorithm')
         x, k, trace = ek.brent(evaluate, small_k, big_k)
         print(f'Optimal K is {x}')
-        out = dict(x=x, trace=[dict(K=kf, int_K=ki, labelled_acc=a) for kf, ki, a in trace])
-    else:
+        out = dict(x=x, trace=[{'K': kf, 'int_K': ki, name: a} for kf, ki, a in trace])
+    elif args.search_mode == 'binary':
         k, trace = ek.binary_search(evaluate, small_k, big_k, log=print)
         out = dict(trace=[dict(small_k=s, middle_k=m, big_k=b, accs=list(a)) for s, m, b, a in trace])
-    out.update(k=int(k), search_mode=args.search_mode, min_classes=int(small_k), max_classes=int(big_k),
+    else:
+        k, trace = ek.grid_search(evaluate, small_k, big_k, log=print)
+        out = dict(trace=[dict(ks=list(ks), scores=list(sc), best=int(b)) for ks, sc, b in trace])
+    out.update(k=int(k), criterion=args.criterion, search_mode=args.search_mode, min_classes=int(small_k), max_classes=int(big_k),
                scores={str(kk): v for kk, v in sorted(scores.items())})
     cdir = os.path.join(args.root_dir, 'cluster')
     os.makedirs(cdir, exist_ok=True)

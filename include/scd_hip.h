@@ -378,6 +378,22 @@ size_t scd_contingency_stats_ws_bytes(int s, int kp, int kt);
 int scd_contingency_stats(scd_handle h, const int32_t* table, int s, int kp, int kt, int64_t* ints_out, double* info_out, void* ws,
                           size_t ws_bytes, void* stream);
 
+/* ---- silhouette coefficients: sklearn.metrics.silhouette_samples(X, labels, metric='euclidean') and their mean, the label-free
+ * criterion of the search for the number of categories (docs/design/estimate_k.md).  X [n, d] (SCD_F32 or SCD_F16), labels int32 [n].
+ * Row i: a = the mean distance to the OTHER rows of its cluster (the sum runs over the cluster, the pair i = i contributes exactly 0,
+ * divided by cnt - 1), b = the smallest mean distance to the rows of another non-empty cluster, s = (b - a) / max(a, b); s = 0 in a
+ * singleton cluster and when max(a, b) = 0.  Label ids without rows are skipped.  samples_out float [n] in the caller's row order,
+ * mean_out double [1] = their mean, info_out int64 [2] = {rows with a label outside [0, k) - they take part in nothing and get s = 0;
+ * the number of non-empty clusters}.  With fewer than two non-empty clusters the outputs are zeros and the call returns SCD_OK.
+ * Arithmetic: rows as fp16 (fp32 input rounded to nearest even), dots accumulated in fp32 by MFMA, dist^2 = max(0, |x_i|^2 + |x_j|^2 -
+ * 2 dot) with the fp32 norms of the fp16 rows, the pair i = j excluded by index, per-cluster sums in fp32, the mean in float64 over a
+ * fixed partition and tree.  No floating-point atomics: two calls on one input return the same bits.
+ * Limits: 2 <= n <= 2^30, 1 <= d <= 1024, 2 <= k <= n; scd_silhouette_ws_bytes returns 0 outside them.  The workspace holds the
+ * label-sorted fp16 copy of X: about 2 n (d rounded up to 64) bytes. */
+size_t scd_silhouette_ws_bytes(int64_t n, int d, int k);
+int scd_silhouette(scd_handle h, const void* X, int x_dtype, const int32_t* labels, int64_t n, int d, int k, float* samples_out,
+                   double* mean_out, int64_t* info_out, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- host solvers (CPU, synchronous) ---- */
 /* linear_assignment (gcd/project_utils/cluster_utils.py:234-493), same tie-breaking; pairs_out [min(n,m),2] sorted */
 int scd_munkres(const int64_t* cost, int n, int m, int64_t* pairs_out, int* n_pairs_out);

@@ -127,6 +127,9 @@ SIGNATURES = {
     "scd_contingency_stats_ws_bytes": (_sz, [_i, _i, _i]),
     # h, table, s, kp, kt, ints_out, info_out, ws, ws_bytes, stream
     "scd_contingency_stats": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    "scd_silhouette_ws_bytes": (_sz, [_i64, _i, _i]),
+    # h, X, x_dtype, labels, n, d, k, samples_out, mean_out, info_out, ws, ws_bytes, stream
+    "scd_silhouette": (_i, [_vp, _vp, _i, _vp, _i64, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "scd_munkres": (_i, [_vp, _i, _i, _vp, C.POINTER(_i)]),
     "scd_munkres_sparse": (_i, [_i, _i64, _vp, _vp, _vp, _vp, C.POINTER(_i)]),
     "scd_transport_solve": (_i, [_vp, _i64, _i, _i, _i, _vp, C.POINTER(_i64)]),

@@ -6,7 +6,13 @@ sequence of K, and keep the K whose clustering accuracy on the LABELLED rows is 
   * `binary_search` restates estimate_k.py:172-218 decision for decision;
   * `brent`         restates `scipy_optimise`, estimate_k.py:221-242 (scipy's bounded Brent on -ACC).
 
-Both searches memoise their evaluations by int(K).  The fit is deterministic for a fixed K (random_state=0, deterministic kernels), so
+Without labelled rows (main_unsup.py's setting) there is nothing to take an accuracy on:
+
+  * `evaluate_k_unlabelled` scores a fit by its mean silhouette coefficient (metrics.silhouette_score: scd_silhouette on the device);
+  * `grid_search`           is an integer search for it - bounded Brent on an integer-truncated K is fragile for this criterion
+                            (docs/design/estimate_k.md, "Without labels").
+
+All searches memoise their evaluations by int(K).  The fit is deterministic for a fixed K (random_state=0, deterministic kernels), so
 an evaluation repeated at the same K would return the same accuracy: memoising changes no decision of either search, it only saves
 the repeated fits (bounded Brent on an integer-truncated K revisits the same int(K) several times near its end).
 """
@@ -34,6 +40,20 @@ def evaluate_k(K, feats, targets, mask_lab, verbose=False, **kmeans_kw):
             if s is not None:
                 print('{} Instances acc {:.4f}, nmi {:.4f}, ari {:.4f}'.format(name, s['acc'], s['nmi'], s['ari']))
     return scores["labelled"]["acc"], scores
+
+
+def evaluate_k_unlabelled(K, feats, verbose=False, **kmeans_kw):
+    """One K of the label-free search: fit `KMeans(n_clusters=K, random_state=0)` on feats (device float32 / float16 [n, d]) and score
+    `labels_device_` by the mean silhouette coefficient on the device.  Returns (silhouette, {'silhouette': s}); neither the labels nor
+    the features leave the device."""
+    K = int(K)
+    kw = dict(random_state=0)
+    kw.update(kmeans_kw)
+    km = KMeans(n_clusters=K, **kw).fit(feats)
+    s = metrics.silhouette_score(feats, km.labels_device_)
+    if verbose:
+        print('K = {}: silhouette {:.4f}'.format(K, s))
+    return s, {'silhouette': s}
 
 
 class _Memo:
@@ -109,3 +129,35 @@ def brent(evaluate, small_k, big_k):
 
     res = minimize_scalar(neg_acc, bounds=(small_k, big_k), method='bounded')
     return float(res.x), int(res.x), trace
+
+
+def grid_search(evaluate, small_k, big_k, points=9, log=None):
+    """Integer search for the K in [small_k, big_k] that maximises evaluate(K).  Each round lays `m = min(points, hi - lo + 1)` integers
+    evenly over [lo, hi] (ends included, rounded to nearest), evaluates them all (memoised) and takes the FIRST maximum, so the lowest K
+    wins a tie.  If the round's K are consecutive integers that K is the answer; otherwise the interval shrinks to the grid neighbours
+    below and above the best (clamped at the ends) and the search repeats.  (With three points and the best in the middle those
+    neighbours are the interval's own ends; the interval then shrinks to the midpoints between the best and its neighbours.)
+    Deterministic.  Returns (best_k, trace) with trace[r] = (ks, scores, best)."""
+    small_k, big_k, points = int(small_k), int(big_k), int(points)
+    if big_k <= small_k:
+        raise ValueError("grid_search needs small_k < big_k (got %d, %d)" % (small_k, big_k))
+    if points < 3:
+        raise ValueError("grid_search needs points >= 3 (got %d)" % points)
+    ev = _Memo(evaluate)
+    log = log or (lambda s: None)
+    trace = []
+    lo, hi = small_k, big_k
+    while True:
+        m = min(points, hi - lo + 1)
+        ks = sorted({lo + ((hi - lo) * i + (m - 1) // 2) // (m - 1) for i in range(m)})
+        scores = [ev(K) for K in ks]
+        b = max(range(len(ks)), key=lambda i: (scores[i], -i))
+        best = ks[b]
+        trace.append((ks, scores, best))
+        log('Round %d: K %s -> best %d (%.4f)' % (len(trace) - 1, ks, best, scores[b]))
+        if ks[-1] - ks[0] == len(ks) - 1:
+            return best, trace
+        below, above = ks[max(b - 1, 0)], ks[min(b + 1, len(ks) - 1)]
+        if (below, above) == (lo, hi):
+            below, above = (below + best + 1) // 2, (best + above) // 2
+        lo, hi = below, above

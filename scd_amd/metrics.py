@@ -12,6 +12,9 @@ The label arrays stay on the device; a call reads back S x 6 integers and S x 3 
 NMI / ARI / purity are pure functions of those statistics (`nmi_from_stats`, `ari_from_stats`, `purity_from_stats`).
 
 Tables are indexed [pred, truth]: a_i (row sums) belong to the predictions, b_j (column sums) to the targets.
+
+`silhouette_samples` / `silhouette_score` need no targets: scikit-learn's functions of those names (metric='euclidean') through
+scd_silhouette, one n x n x d MFMA pass; features and labels stay on the device.
 """
 import numpy as np
 import torch
@@ -148,3 +151,46 @@ def score_split(pred, truth, labelled_mask):
         out[name] = dict(acc=_acc_from_table(w[s]), nmi=nmi_from_stats(ints[s], info[s]), ari=ari_from_stats(ints[s]),
                          purity=purity_from_stats(ints[s]))
     return out
+
+
+# ------------------------------------------------------------------ silhouette (no targets)
+def _silhouette(X, labels, k=None):
+    if not torch.is_tensor(X):
+        X = torch.from_numpy(np.ascontiguousarray(np.asarray(X)))
+        if X.dtype not in (torch.float16, torch.float32):
+            X = X.float()
+    if X.dim() != 2:
+        raise ValueError("X must be [n_samples, n_features]")
+    if not X.is_cuda:
+        X = X.to(labels.device if torch.is_tensor(labels) and labels.is_cuda else "cuda")
+    if X.dtype not in (torch.float16, torch.float32):
+        X = X.float()
+    labels = _labels(labels, X.device)
+    n = X.shape[0]
+    if labels.numel() != n:
+        raise ValueError("X has %d rows, labels %d" % (n, labels.numel()))
+    if n < 2:
+        raise ValueError("the silhouette needs at least 2 rows")
+    k = int(labels.max().item()) + 1 if k is None else int(k)
+    if k > n:                       # an id this large cannot come from a clustering of n rows with ids [0, k): more ids than rows
+        raise ValueError("labels reach %d on %d rows: label ids must lie in [0, n_samples)" % (k - 1, n))
+    samples, mean, info = ops.silhouette(X, labels, max(k, 2))
+    bad, n_labels = (int(v) for v in info.cpu().numpy())
+    if bad:
+        raise ValueError("%d rows have a label outside [0, %d)" % (bad, max(k, 2)))
+    if not 1 < n_labels < n:
+        raise ValueError("Number of labels is %d. Valid values are 2 to n_samples - 1 (inclusive)" % n_labels)
+    return samples, mean
+
+
+def silhouette_samples(X, labels, k=None):
+    """sklearn.metrics.silhouette_samples(X, labels, metric='euclidean') as a device float32 vector [n] in X's row order.  X: device
+    fp16 / fp32 tensor or numpy [n, d] (used as fp16: fp32 is rounded to nearest); labels: integers in [0, k), ids without rows
+    allowed; k defaults to labels.max() + 1.  ValueError on a label outside [0, k) and unless 1 < non-empty clusters < n
+    (scikit-learn's check)."""
+    return _silhouette(X, labels, k)[0]
+
+
+def silhouette_score(X, labels, k=None):
+    """sklearn.metrics.silhouette_score(X, labels, metric='euclidean'): the mean of silhouette_samples, summed in float64 on the device."""
+    return float(_silhouette(X, labels, k)[1].item())

@@ -863,6 +863,27 @@ def contingency_stats(table):
     return ints, info
 
 
+def silhouette(x, labels, k):
+    """scd_silhouette: x fp16 / fp32 [n, d] and labels int32 [n] on the device -> (samples float32 [n] in x's row order, mean float64
+    [1], info int64 [2] = rows with a label outside [0, k), non-empty clusters), all on the device.  Fewer than two non-empty clusters
+    give zeros; the callers in scd_amd.metrics raise on that and on a bad label."""
+    _need_cuda(x, labels)
+    if x.dim() != 2 or x.dtype not in (torch.float16, torch.float32) or labels.dtype != torch.int32:
+        raise _lib.ScdError(_lib.SCD_EINVAL, "silhouette: x must be fp16 / fp32 [n, d] and labels int32")
+    x, labels = x.contiguous(), labels.contiguous()
+    n, d = x.shape
+    if labels.numel() != n:
+        raise _lib.ScdError(_lib.SCD_EINVAL, "silhouette: x and labels must have one length")
+    samples = torch.empty(n, dtype=torch.float32, device=x.device)
+    mean = torch.empty(1, dtype=torch.float64, device=x.device)
+    info = torch.empty(2, dtype=torch.int64, device=x.device)
+    nb = _L().scd_silhouette_ws_bytes(n, d, int(k))
+    ws = _ws(max(nb, 16), x.device)
+    dt = SCD_F32 if x.dtype == torch.float32 else SCD_F16
+    check(_L().scd_silhouette(handle(), ptr(x), dt, ptr(labels), n, d, int(k), ptr(samples), ptr(mean), ptr(info), ptr(ws), nb, stream_ptr()))
+    return samples, mean, info
+
+
 # ----------------------------------------------------------------------------- host solvers
 def munkres(cost):
     """linear_assignment (cluster_utils.py:234): int array [n,m] -> sorted pairs [min(n,m),2]."""
