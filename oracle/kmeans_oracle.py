@@ -153,8 +153,25 @@ def kpp_draw(d2_f32, r):
     return int(hit[0]) if hit.size else -1
 
 
-def kpp(x, pre_centers, k, random_state, trace=None):
-    """K_Means.kpp (sskm_constrained.py:28-44 / faster_mix...:82-110)."""
+def rule_p(d2_f32):
+    """Is the draw from d2 independent of the order of additions?  prob = float32(d2 / float32(sum)) must consist of multiples of
+    2^-52 with a total below 2: every partial sum of them, in any association, is then an exact float64, and kpp_draw's sequential
+    cumsum is the one right answer (every non-zero d2 >= 2^-28 sum(d2) is sufficient).  Asserts that and returns the smallest
+    non-zero d2 / sum(d2) (inf when there is none)."""
+    d2 = np.asarray(d2_f32, dtype=F32)
+    tot = F32(np.sum(d2.astype(F64)))
+    assert np.isfinite(tot) and tot > 0, "rule P: the sum must be finite and positive"
+    prob = (d2 / tot).astype(F32).astype(F64)
+    scaled = prob * 2.0 ** 52
+    assert np.array_equal(scaled, np.floor(scaled)), "rule P: a probability is no multiple of 2^-52"
+    assert float(np.sum(np.floor(scaled))) < 2.0 ** 53, "rule P: the probabilities sum to 2 or more"
+    nz = d2[d2 > 0]
+    return float(nz.min().astype(F64) / np.sum(d2.astype(F64))) if nz.size else float("inf")
+
+
+def kpp(x, pre_centers, k, random_state, trace=None, before_draw=None):
+    """K_Means.kpp (sskm_constrained.py:28-44 / faster_mix...:82-110).  before_draw (tests): called with the float32 distances of
+    every round before its draw (e.g. rule_p)."""
     rs = check_random_state(random_state)
     x = np.asarray(x, dtype=F32)
     if pre_centers is not None:
@@ -164,6 +181,8 @@ def kpp(x, pre_centers, k, random_state, trace=None):
     d2 = pairwise_distance64(x, c).min(axis=1)
     while c.shape[0] < k:
         r = rs.rand()
+        if before_draw is not None:
+            before_draw(d2.astype(F32))
         ind = kpp_draw(d2.astype(F32), r)
         if ind < 0:
             raise IndexError("k-means++ draw fell off the end of cum_prob")
