@@ -14,7 +14,7 @@ All features, labelled and unlabelled, are L2-normalised once (estimate_k.py:61)
 Fits and scores run on the GPU (scd_amd.cluster.KMeans, scd_amd.metrics).  Writes
 ROOT/cluster/estimated_k_{feat_model}_{dataset_name}.json and prints the value to pass as --n_cluster.
 
-  python estimate_k.py --root_dir ROOT --dataset_name cub --feat_model clip [--max_classes 1000] [--search_mode brent|binary|grid]
+  python estimate_k.py --root_dir ROOT --dataset_name cub --feat_model clip [--max_classes 1000] [--search_mode brent|binary|grid|finch]
   python estimate_k.py --root_dir ROOT --dataset_name D --feat_model clip --criterion silhouette --max_classes 1000
 """
 import argparse
@@ -39,8 +39,9 @@ def build_parser():
                         'silhouette - 2')
     p.add_argument('--criterion', type=str, default='acc', choices=['acc', 'silhouette'],
                    help='acc: clustering accuracy on the labelled rows (GCD); silhouette: mean silhouette coefficient, needs no labels')
-    p.add_argument('--search_mode', type=str, default=None, choices=['brent', 'binary', 'grid'],
-                   help='Mode for black box optimisation; default: brent for acc, grid for silhouette')
+    p.add_argument('--search_mode', type=str, default=None, choices=['brent', 'binary', 'grid', 'finch'],
+                   help='Mode for black box optimisation; default: brent for acc, grid for silhouette.  finch: score only the '
+                        'cluster counts of FINCH\'s partitions of all rows, clipped to [min_classes, max_classes]')
     return p
 
 
@@ -99,6 +100,12 @@ def main(argv=None):
     elif args.search_mode == 'binary':
         k, trace = ek.binary_search(evaluate, small_k, big_k, log=print)
         out = dict(trace=[dict(small_k=s, middle_k=m, big_k=b, accs=list(a)) for s, m, b, a in trace])
+    elif args.search_mode == 'finch':
+        from scd_amd.finch import Finch
+        finch_num_clust = [int(v) for v in Finch().fit(feats).num_clust_]
+        print(f'FINCH partitions: {finch_num_clust} clusters')
+        k, trace = ek.finch_search(evaluate, finch_num_clust, small_k, big_k, log=print)
+        out = dict(trace=[dict(ks=list(ks), scores=list(sc), best=int(b)) for ks, sc, b in trace], finch_num_clust=finch_num_clust)
     else:
         k, trace = ek.grid_search(evaluate, small_k, big_k, log=print)
         out = dict(trace=[dict(ks=list(ks), scores=list(sc), best=int(b)) for ks, sc, b in trace])

@@ -394,6 +394,34 @@ size_t scd_silhouette_ws_bytes(int64_t n, int d, int k);
 int scd_silhouette(scd_handle h, const void* X, int x_dtype, const int32_t* labels, int64_t n, int d, int k, float* samples_out,
                    double* mean_out, int64_t* info_out, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- FINCH first-neighbour clustering, cosine distance (local_utils/finch.py; docs/design/finch.md) ---- */
+/* clust_rank's first neighbours (finch.py:24-27) without the n x n matrix: nn_out[i] = argmax over j != i of dot(U_i, U_j), the dot
+ * taken in float64 on the fp32 rows U [n, d], ties to the lowest j (fill_diagonal + argmin); d1_out[i] = 1 - that dot (float64).  U need
+ * not be unit.  An fp16 MFMA pass with an error bound computed from the rows filters the columns, float64 decides; a row whose
+ * certificate fails takes an exact pass over all columns.  info_out int32 [2] = {rows that took the exact full-row pass, 1 if a value did
+ * not fit fp16 (then every row takes it)}.  The result never depends on the filter; two calls return the same bits.
+ * Limits: 2 <= n < 2^31 (n = 1: SCD_EINVAL), 1 <= d with d rounded up to 32 <= 1024; scd_first_neighbor_ws_bytes returns 0 outside
+ * them.  The workspace holds the fp16 copy of U: about 2 n (d rounded up to 64) bytes, plus 132 bytes per row and column range. */
+size_t scd_first_neighbor_ws_bytes(int64_t n, int d);
+int scd_first_neighbor(scd_handle h, const float* U, int64_t n, int d, int32_t* nn_out, double* d1_out, int32_t* info_out, void* ws,
+                       size_t ws_bytes, void* stream);
+/* out[p] = 1 - float64 dot of rows a[p] and b[p] of U [n, d] (the same dot as scd_first_neighbor's): the distances between rows that share
+ * a first neighbour (min_sim, finch.py:138-139) and across a cut mutual pair (:49-50).  A pair with an index outside [0, n) gives NaN. */
+int scd_pair_dist_f64(scd_handle h, const float* U, int64_t n, int d, const int32_t* a, const int32_t* b, int64_t m, double* out,
+                      void* stream);
+/* get_clust's connected_components (finch.py:52) on an undirected edge list (ea[e], eb[e]), e < m: labels_out int32 [n] numbered by the
+ * rank of each component's lowest member (scipy's order), ncomp_out int32 [1].  Hooking onto the smaller index and pointer jumping until
+ * a device-side change flag stays clear; integers only, the result does not depend on the order of the steps.  Synchronises the stream
+ * (it reads the flag).  An edge end outside [0, n) is SCD_EINVAL.  m = 0 gives n singletons. */
+size_t scd_link_components_ws_bytes(int64_t n);
+int scd_link_components(scd_handle h, int64_t n, const int32_t* ea, const int32_t* eb, int64_t m, int32_t* labels_out, int32_t* ncomp_out,
+                        void* ws, size_t ws_bytes, void* stream);
+/* cool_mean (finch.py:56-69) for k segments: segment c holds the rows order[offsets[c] .. offsets[c + 1]) of X [n, d] (order: the stable
+ * sort of the rows by label).  mean_out[c] = the float64 sum of those rows in that order, divided by the count, rounded to fp32;
+ * unit_out[c] = the mean divided by its norm (taken in float64), the next level's rows; a zero mean stays zero. */
+int scd_segment_mean_unit(scd_handle h, const float* X, int64_t n, const int32_t* order, const int64_t* offsets, int k, int d,
+                          float* mean_out, float* unit_out, void* stream);
+
 /* ---- host solvers (CPU, synchronous) ---- */
 /* linear_assignment (gcd/project_utils/cluster_utils.py:234-493), same tie-breaking; pairs_out [min(n,m),2] sorted */
 int scd_munkres(const int64_t* cost, int n, int m, int64_t* pairs_out, int* n_pairs_out);

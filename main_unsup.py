@@ -56,7 +56,7 @@ def build_parser():
     p.add_argument('--transform', type=str, default='imagenet')
     p.add_argument('--extract_feat', type=str2bool, default=False)
     p.add_argument('--run_cluster', type=str2bool, default=False)
-    p.add_argument('--cluster', type=str, default='KM', help='options: KM, SSKM, ConSSKM')
+    p.add_argument('--cluster', type=str, default='KM', help='options: KM, SSKM, ConSSKM, FINCH (first-neighbour clustering refined to --n_cluster clusters)')
     p.add_argument('--save_cluster', type=str2bool, default=False)
     p.add_argument('--n_cluster', type=int, default=1000)
     p.add_argument('--cluster_size_min', type=int, default=50)
@@ -88,6 +88,11 @@ def run_clustering(args, u_feats, l_feats, l_targets):
     elif args.cluster == 'KM':
         # :362 `KMeans(n_clusters=args.n_cluster, random_state=0).fit(u_feats).labels_` - on the device, no host sklearn
         return None, KMeans(n_clusters=args.n_cluster, random_state=0).fit(np.asarray(u_feats, dtype=np.float32)).labels_
+    elif args.cluster == 'FINCH':
+        # no K-dependent fit: the first-neighbour hierarchy on the unlabelled rows, then req_clust = n_cluster (local_utils/finch.py:164-171)
+        from scd_amd.local_utils.finch import FINCH
+        _, _, req_c = FINCH(np.asarray(u_feats, dtype=np.float32), req_clust=args.n_cluster, verbose=True)
+        return None, req_c.astype(np.int64)
     else:
         raise NotImplementedError(args.cluster)
     u, l, lt = (torch.as_tensor(x).to(dev) for x in (u_feats, l_feats, l_targets))

@@ -130,6 +130,16 @@ SIGNATURES = {
     "scd_silhouette_ws_bytes": (_sz, [_i64, _i, _i]),
     # h, X, x_dtype, labels, n, d, k, samples_out, mean_out, info_out, ws, ws_bytes, stream
     "scd_silhouette": (_i, [_vp, _vp, _i, _vp, _i64, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "scd_first_neighbor_ws_bytes": (_sz, [_i64, _i]),
+    # h, U, n, d, nn_out, d1_out, info_out, ws, ws_bytes, stream
+    "scd_first_neighbor": (_i, [_vp, _vp, _i64, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    # h, U, n, d, a, b, m, out, stream
+    "scd_pair_dist_f64": (_i, [_vp, _vp, _i64, _i, _vp, _vp, _i64, _vp, _vp]),
+    "scd_link_components_ws_bytes": (_sz, [_i64]),
+    # h, n, ea, eb, m, labels_out, ncomp_out, ws, ws_bytes, stream
+    "scd_link_components": (_i, [_vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _sz, _vp]),
+    # h, X, n, order, offsets, k, d, mean_out, unit_out, stream
+    "scd_segment_mean_unit": (_i, [_vp, _vp, _i64, _vp, _vp, _i, _i, _vp, _vp, _vp]),
     "scd_munkres": (_i, [_vp, _i, _i, _vp, C.POINTER(_i)]),
     "scd_munkres_sparse": (_i, [_i, _i64, _vp, _vp, _vp, _vp, C.POINTER(_i)]),
     "scd_transport_solve": (_i, [_vp, _i64, _i, _i, _i, _vp, C.POINTER(_i64)]),

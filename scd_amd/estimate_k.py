@@ -12,6 +12,9 @@ Without labelled rows (main_unsup.py's setting) there is nothing to take an accu
   * `grid_search`           is an integer search for it - bounded Brent on an integer-truncated K is fragile for this criterion
                             (docs/design/estimate_k.md, "Without labels").
 
+  * `finch_search`          scores only the cluster counts FINCH's partitions propose (scd_amd.finch; docs/design/finch.md): a
+                            handful of fits instead of a sweep.
+
 All searches memoise their evaluations by int(K).  The fit is deterministic for a fixed K (random_state=0, deterministic kernels), so
 an evaluation repeated at the same K would return the same accuracy: memoising changes no decision of either search, it only saves
 the repeated fits (bounded Brent on an integer-truncated K revisits the same int(K) several times near its end).
@@ -161,3 +164,21 @@ def grid_search(evaluate, small_k, big_k, points=9, log=None):
         if (below, above) == (lo, hi):
             below, above = (below + best + 1) // 2, (best + above) // 2
         lo, hi = below, above
+
+
+def finch_search(evaluate, candidates, small_k, big_k, log=None):
+    """The K among FINCH's cluster counts that maximises evaluate(K).  `candidates` (FINCH's num_clust) are clipped to
+    [small_k, big_k]; the distinct values are evaluated in increasing order (memoised) and the FIRST maximum wins, so the lowest K wins
+    a tie - grid_search's rule.  Returns (best_k, trace) with trace[0] = (ks, scores, best).  No candidate: ValueError."""
+    small_k, big_k = int(small_k), int(big_k)
+    if big_k < small_k:
+        raise ValueError("finch_search needs small_k <= big_k (got %d, %d)" % (small_k, big_k))
+    ks = sorted({min(max(int(k), small_k), big_k) for k in candidates})
+    if not ks:
+        raise ValueError("finch_search: FINCH proposed no cluster count")
+    ev = _Memo(evaluate)
+    log = log or (lambda s: None)
+    scores = [ev(K) for K in ks]
+    b = max(range(len(ks)), key=lambda i: (scores[i], -i))
+    log('FINCH candidates: K %s -> best %d (%.4f)' % (ks, ks[b], scores[b]))
+    return ks[b], [(ks, scores, ks[b])]

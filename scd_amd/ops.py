@@ -884,6 +884,67 @@ def silhouette(x, labels, k):
     return samples, mean, info
 
 
+# ----------------------------------------------------------------------------- FINCH primitives (docs/design/finch.md)
+def first_neighbor(u):
+    """scd_first_neighbor: u float32 [n, d] on the device -> (nn int32 [n], d1 float64 [n], info int32 [2] = rows through the exact
+    full-row pass, fp16-overflow flag), all on the device.  nn[i] = argmax over j != i of the float64 dot of rows i and j, ties to the
+    lowest j; d1 = 1 - that dot."""
+    _need_cuda(u)
+    if u.dim() != 2 or u.dtype != torch.float32:
+        raise _lib.ScdError(_lib.SCD_EINVAL, "first_neighbor: u must be float32 [n, d]")
+    u = u.contiguous()
+    n, d = u.shape
+    nn = torch.empty(n, dtype=torch.int32, device=u.device)
+    d1 = torch.empty(n, dtype=torch.float64, device=u.device)
+    info = torch.empty(2, dtype=torch.int32, device=u.device)
+    nb = _L().scd_first_neighbor_ws_bytes(n, d)
+    ws = _ws(max(nb, 16), u.device)
+    check(_L().scd_first_neighbor(handle(), ptr(u), n, d, ptr(nn), ptr(d1), ptr(info), ptr(ws), nb, stream_ptr()))
+    return nn, d1, info
+
+
+def pair_dist_f64(u, a, b):
+    """scd_pair_dist_f64: 1 - float64 dot of rows a[p] and b[p] of u float32 [n, d]; a, b int32 [m] on the device -> float64 [m]."""
+    _need_cuda(u, a, b)
+    if u.dim() != 2 or u.dtype != torch.float32 or a.dtype != torch.int32 or b.dtype != torch.int32 or a.numel() != b.numel():
+        raise _lib.ScdError(_lib.SCD_EINVAL, "pair_dist_f64: u must be float32 [n, d], a and b int32 of one length")
+    u, a, b = u.contiguous(), a.contiguous(), b.contiguous()
+    out = torch.empty(a.numel(), dtype=torch.float64, device=u.device)
+    check(_L().scd_pair_dist_f64(handle(), ptr(u), u.shape[0], u.shape[1], ptr(a), ptr(b), a.numel(), ptr(out), stream_ptr()))
+    return out
+
+
+def link_components(n, ea, eb):
+    """scd_link_components: the connected components of the undirected edges (ea[e], eb[e]) (device int32 [m]) on n nodes ->
+    (labels int32 [n] numbered by the rank of each component's lowest member, the number of components as an int)."""
+    _need_cuda(ea, eb)
+    if ea.dtype != torch.int32 or eb.dtype != torch.int32 or ea.numel() != eb.numel():
+        raise _lib.ScdError(_lib.SCD_EINVAL, "link_components: ea and eb must be int32 of one length")
+    ea, eb = ea.contiguous(), eb.contiguous()
+    labels = torch.empty(int(n), dtype=torch.int32, device=ea.device)
+    ncomp = torch.empty(1, dtype=torch.int32, device=ea.device)
+    nb = _L().scd_link_components_ws_bytes(int(n))
+    ws = _ws(max(nb, 16), ea.device)
+    check(_L().scd_link_components(handle(), int(n), ptr(ea), ptr(eb), ea.numel(), ptr(labels), ptr(ncomp), ptr(ws), nb, stream_ptr()))
+    return labels, int(ncomp.item())
+
+
+def segment_mean_unit(x, order, offsets):
+    """scd_segment_mean_unit: x float32 [n, d], order int32 [n] (the stable sort of the rows by label), offsets int64 [k + 1] ->
+    (means float32 [k, d]: float64 sums in row order / count; their unit rows float32 [k, d], the norm in float64)."""
+    _need_cuda(x, order, offsets)
+    if x.dim() != 2 or x.dtype != torch.float32 or order.dtype != torch.int32 or offsets.dtype != torch.int64 or offsets.numel() < 2:
+        raise _lib.ScdError(_lib.SCD_EINVAL, "segment_mean_unit: x float32 [n, d], order int32, offsets int64 [k + 1]")
+    x, order, offsets = x.contiguous(), order.contiguous(), offsets.contiguous()
+    k, d = offsets.numel() - 1, x.shape[1]
+    if order.numel() != x.shape[0]:
+        raise _lib.ScdError(_lib.SCD_EINVAL, "segment_mean_unit: order must hold one entry per row of x")
+    mean = torch.empty((k, d), dtype=torch.float32, device=x.device)
+    unit = torch.empty((k, d), dtype=torch.float32, device=x.device)
+    check(_L().scd_segment_mean_unit(handle(), ptr(x), x.shape[0], ptr(order), ptr(offsets), k, d, ptr(mean), ptr(unit), stream_ptr()))
+    return mean, unit
+
+
 # ----------------------------------------------------------------------------- host solvers
 def munkres(cost):
     """linear_assignment (cluster_utils.py:234): int array [n,m] -> sorted pairs [min(n,m),2]."""
