@@ -34,10 +34,21 @@ static_assert(sizeof(PrepHdr) == 64, "PrepHdr must be 64 bytes");
 
 static inline int dpad(int d) { return (d + 127) / 128 * 128; }
 
-extern "C" size_t scd_kmeans_prep_bytes(int64_t n, int d) {
-    size_t dp = dpad(d);
-    return scd_align(64 + 8 * dp) + scd_align(4 * (size_t)n) + scd_align(2 * ((size_t)n + 32) * dp) + 256;   // + one unit of padding (estep_stream_kernel)
+// the one place that computes offsets into the prepared data set
+struct PrepLayout {
+    PrepHdr* hdr; double* mu; float* xnorm; half_t* xh;
+    size_t xnorm_off, xh_off, bytes;
+};
+static inline PrepLayout prep_layout(const void* base, int64_t n, int dp) {
+    char* p = (char*)base;
+    PrepLayout l;
+    l.xnorm_off = scd_align(64 + 8 * (size_t)dp);
+    l.xh_off = l.xnorm_off + scd_align(4 * (size_t)n);
+    l.bytes = l.xh_off + scd_align(2 * ((size_t)n + 32) * dp) + 256;   // + one unit of padding (estep_stream_kernel)
+    l.hdr = (PrepHdr*)p; l.mu = (double*)(p + 64); l.xnorm = (float*)(p + l.xnorm_off); l.xh = (half_t*)(p + l.xh_off);
+    return l;
 }
+extern "C" size_t scd_kmeans_prep_bytes(int64_t n, int d) { return prep_layout(nullptr, n, dpad(d)).bytes; }
 
 // column sums in float64: block (0..gridDim.x) strides over rows, thread t owns columns t, t+256, ...
 __global__ void __launch_bounds__(256) colsum_kernel(const float* __restrict__ X, long long n, int d, double* mu) {
@@ -96,19 +107,19 @@ extern "C" int scd_kmeans_prepare(scd_handle h, const float* X, int64_t n, int d
     const int dp = dpad(d);
     PrepHdr hh = {};
     hh.d = d; hh.dp = dp; hh.n = n;
-    hh.xnorm_off = scd_align(64 + 8 * (size_t)dp);
-    hh.xh_off = hh.xnorm_off + scd_align(4 * (size_t)n);
+    const PrepLayout pl = prep_layout(prep, n, dp);
+    hh.xnorm_off = pl.xnorm_off;
+    hh.xh_off = pl.xh_off;
     char* p = (char*)prep;
     SCD_HIP(hipMemsetAsync(p, 0, 64 + 8 * (size_t)dp, st));
     SCD_HIP(hipMemcpyAsync(p, &hh, sizeof(hh), hipMemcpyHostToDevice, st));
-    double* mu = (double*)(p + 64);
+    double* mu = pl.mu;
     int blocks = (int)((n < 1024) ? n : 1024);
     colsum_kernel<<<blocks, 256, 0, st>>>(X, n, d, mu);
     mu_finish_kernel<<<(d + 255) / 256, 256, 0, st>>>(mu, d, n);
     maxabs_kernel<<<blocks, 256, 0, st>>>(X, n, d, mu, &((PrepHdr*)p)->maxabs_bits);
     scale_kernel<<<1, 1, 0, st>>>((PrepHdr*)p);
-    center_kernel<<<(unsigned)scd_cdiv(n, 4), 256, 0, st>>>(X, n, d, dp, (const PrepHdr*)p, mu, (float*)(p + hh.xnorm_off),
-                                                             (half_t*)(p + hh.xh_off));
+    center_kernel<<<(unsigned)scd_cdiv(n, 4), 256, 0, st>>>(X, n, d, dp, (const PrepHdr*)p, mu, pl.xnorm, pl.xh);
     SCD_LAUNCH_CHECK();
     return SCD_OK;
 }
@@ -125,10 +136,31 @@ struct EHdr {
 };
 static inline int kpad(int k) { return (k + 127) / 128 * 128; }
 
-extern "C" size_t scd_kmeans_estep_ws_bytes(int64_t n, int d, int k) {
-    size_t kp = kpad(k), dp = dpad(d);
-    return 64 + scd_align(4 * kp) + scd_align(2 * kp * dp) + scd_align(4 * kp * dp) + 3 * scd_align(4 * (size_t)n) + scd_align(2 * kp * dp) + 2 * scd_align(12 * (size_t)n) + 256;
+// the one place that computes offsets into the E-step workspace
+struct EstepWs {
+    EHdr* eh; float* cn; half_t* ch; float* ct; int* flags; int* fcand; int* fulls;
+    half_t* chf;            // centres in MFMA-fragment order (streaming path); 16 bytes per centre of estep_ext_kernel (single-pass path)
+    float* tkey; int* tidx; // [3][n] keys / centres between the passes of K > 128; tkey also the split row blocks' keys (estep_rb_kernel)
+    size_t bytes;
+};
+static inline EstepWs estep_ws_layout(void* base, int64_t n, int dp, int kp) {
+    char* w = (char*)base;
+    const size_t kd = (size_t)kp * dp, a4n = scd_align(4 * (size_t)n), a12n = scd_align(12 * (size_t)n);
+    EstepWs l;
+    l.eh = (EHdr*)w;
+    l.cn = (float*)(w + 64);
+    l.ch = (half_t*)((char*)l.cn + scd_align(4 * (size_t)kp));
+    l.ct = (float*)((char*)l.ch + scd_align(2 * kd));
+    l.flags = (int*)((char*)l.ct + scd_align(4 * kd));
+    l.fcand = (int*)((char*)l.flags + a4n);
+    l.fulls = (int*)((char*)l.fcand + a4n);
+    l.chf = (half_t*)((char*)l.fulls + a4n);
+    l.tkey = (float*)((char*)l.chf + scd_align(2 * kd));
+    l.tidx = (int*)((char*)l.tkey + a12n);
+    l.bytes = (size_t)((char*)l.tidx + a12n - w) + 256;
+    return l;
 }
+extern "C" size_t scd_kmeans_estep_ws_bytes(int64_t n, int d, int k) { return estep_ws_layout(nullptr, n, dpad(d), kpad(k)).bytes; }
 
 // one block per (padded) centre: c' = (c-mu)*scale -> fp16; cn = ||c'||^2 (float64 -> float32)
 // cn doubles as the centre's state: a finite norm below 3.0e38 = live and inside the filters' range; +inf = dead (padding, NaN:
@@ -139,7 +171,7 @@ extern "C" size_t scd_kmeans_estep_ws_bytes(int64_t n, int d, int k) {
 // >= 240,000, a live centre's accumulator drops below the -4 * 60,000 a dead centre gets and a dead centre would take the label.
 // With ||x'|| <= 16 sqrt(Dp) = 362.04 at Dp = 512, ||c'||^2 <= 300 Dp = 153,600 gives 76,800 + 141,890 = 218,690 < 240,000; centres
 // inside the data box have ||c'||^2 < 256 Dp.  So: a live centre with a coordinate beyond fp16 is "wild" on every path, and one with
-// ||c'||^2 > 300 Dp where the extension column exists (Dp = 512, Kp <= 2048: estep_rb_kernel, and estep_rbm_kernel also at Kp = 128);
+// ||c'||^2 > 300 Dp where the extension column exists (Dp = 512, 128 < Kp <= 2048: estep_rb_kernel);
 // the streaming and legacy bounds scale with max ||c'|| and stay valid for long centres, which merely flag more rows there.  A
 // wild centre is dead to the filter (zero operand, never in a triple), and every decision stage that sees one sends EVERY row of the
 // call to the exact all-centres refine, which reads the float32 centres: slow, exact, and reachable only from outside the box.
@@ -215,25 +247,31 @@ __global__ void __launch_bounds__(256) ct_transpose_kernel(const float* __restri
         if (j < dp && c < kp) ct[(size_t)j * kp + c] = t[tx][ty + 8 * i];
     }
 }
+// Which filter serves (dp, kp): the one place that reads SCD_ESTEP_STREAM / SCD_ESTEP_RB (once per process).  scd_kmeans_estep dispatches
+// on it, and finalize_impl derives from it which centre operands the next call will read.
+//   ESTEP_RB      single-pass filter, 128 < Kp <= 2048 at Dp = 512 (estep_rb_kernel)
+//   ESTEP_STREAM  streaming filter, Kp <= 2048 and Dp <= 768 (estep_stream_kernel)
+//   ESTEP_LEGACY  everything else (estep_mfma_kernel)
+enum EstepPath { ESTEP_LEGACY, ESTEP_STREAM, ESTEP_RB };
+static EstepPath estep_path(int dp, int kp) {
+    static const int use_stream = getenv("SCD_ESTEP_STREAM") ? atoi(getenv("SCD_ESTEP_STREAM")) : 1;
+    static const int use_rb = getenv("SCD_ESTEP_RB") ? atoi(getenv("SCD_ESTEP_RB")) : 1;
+    if (use_stream && use_rb && dp == 512 && kp > 128 && kp <= 2048) return ESTEP_RB;
+    if (use_stream && kp <= 2048 && dp <= 768) return ESTEP_STREAM;
+    return ESTEP_LEGACY;
+}
 // many centres: the transposed copy by ct_transpose_kernel behind the per-centre blocks instead of from inside them
 static inline bool ct_separate(int kp) { return kp >= 512; }
 // Only estep_refine_full_kernel reads the transposed copy: the legacy path (Kp > 2048 or Dp > 768).  The single-pass and the streaming
 // path re-evaluate rows against the row-major centres (refine_full_row), so there the copy is not written at all (2 MB of scattered
 // writes per E-step at K = 1000).
-static inline bool ct_dead(int dp, int kp) {
-    static const int use_stream = getenv("SCD_ESTEP_STREAM") ? atoi(getenv("SCD_ESTEP_STREAM")) : 1;
-    return use_stream && kp <= 2048 && dp <= 768;
-}
+static inline bool ct_dead(int dp, int kp) { return estep_path(dp, kp) != ESTEP_LEGACY; }
 // what the per-centre blocks are handed / whether the tiled transpose follows them
 static inline float* ct_inline(float* ct, int dp, int kp) { return (ct_dead(dp, kp) || ct_separate(kp)) ? nullptr : ct; }
 static inline bool ct_after(int dp, int kp) { return !ct_dead(dp, kp) && ct_separate(kp); }
 // the fragment-order copy `chf` serves the streaming filter (K <= 128) only; on the single-pass path of 128 < K <= 2048 at Dp = 512 its
 // place holds 16 bytes per centre written by estep_ext_kernel, so the per-centre blocks do not write it there
-static inline bool chf_unused(int dp, int kp) {
-    static const int use_stream = getenv("SCD_ESTEP_STREAM") ? atoi(getenv("SCD_ESTEP_STREAM")) : 1;
-    static const int use_rb = getenv("SCD_ESTEP_RB") ? atoi(getenv("SCD_ESTEP_RB")) : 1;
-    return use_stream && use_rb && dp == 512 && kp > 128 && kp <= 2048;
-}
+static inline bool chf_unused(int dp, int kp) { return estep_path(dp, kp) == ESTEP_RB; }
 
 __global__ void __launch_bounds__(256) prep_centers_kernel(const float* __restrict__ C, int k, int d, int dp,
                                                            const PrepHdr* hdr, const double* mu, EHdr* eh, float* cn,
@@ -1207,255 +1245,6 @@ __global__ void __launch_bounds__(512) estep_rb_kernel(const half_t* __restrict_
 #undef ERB_MFMA0
 }
 
-// The same sweep for the centres of SEVERAL restarts of one fit at once (scd_kmeans_lloyd_run_multi: the restarts' Lloyd loops in
-// lock-step; faster_mix_k_means_pytorch.py:244-275 runs them one after the other): the rows of a block stay in registers while the centre
-// matrices of the restarts stream past them back to back, `upseg` units (kp / 32) per restart.  A restart is a SEGMENT of the unit
-// stream: its keys carry the centre's index inside the segment, at the segment's end the lane's three best keys are decided exactly as
-// estep_rb_kernel decides (erb_decide's arithmetic) - into one packed register per segment, the selection state is reset - and the label
-// stores / list atomics of all segments happen after the stream has drained (a store inside the loop would sit among the ring fills in
-// the vmcnt queue, and loads and stores do not retire in order with each other: the counted waits would no longer mean "unit u + 1 has
-// landed").  The restarts' E-step workspaces (EHdr | norms | fp16 centres | ... | lists, the layout of scd_kmeans_estep) are equally
-// strided (`ws_stride` bytes from `ws0`), so are their label slots; `segmap` packs the workspace slot of the a-th RUNNING restart in
-// 4-bit fields.  Grid: row blocks x nparts; part p takes the running restarts [p A / nparts, (p + 1) A / nparts) - whole segments, so
-// the parts need no merge.  At most 8 segments and 1,920 centres per part.
-struct RbmArgs {
-    char* ws0; size_t ws_stride;                   // restart slot s: ws0 + s * ws_stride
-    size_t cn_off, ch_off, flags_off, fcand_off, fulls_off;
-    int32_t* lab0; size_t lab_stride;              // labels of slot s: lab0 + s * lab_stride (elements)
-    unsigned long long segmap;
-    int n_active, nparts, kp;
-};
-__global__ void __launch_bounds__(512) estep_rbm_kernel(const half_t* __restrict__ xh, const float* __restrict__ xnorm, const RbmArgs a,
-                                                        long long n) {
-    constexpr int D = 512, UB = 32768, MAXSEG = 8;
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int tid = threadIdx.x;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
-    const int r = lane & 31, hh = lane >> 5;
-    const unsigned sbase = (unsigned)(size_t)(__attribute__((address_space(3))) char*)smem;
-    const int part = (int)blockIdx.x % a.nparts;
-    const long long rblock = blockIdx.x / a.nparts;
-    const int a0 = part * a.n_active / a.nparts, a1 = (part + 1) * a.n_active / a.nparts;
-    const int nseg = a1 - a0, upseg = a.kp >> 5, nunits = nseg * upseg, kp = a.kp;
-    if (nseg <= 0) return;
-    auto slot_of = [&](int sg) { return (int)((a.segmap >> (4 * (a0 + sg))) & 15ull); };
-    float* cm2s = (float*)(smem + 4 * UB + 1920 * 16);            // [MAXSEG] max ||c'||^2 of the part's segments
-
-    // the extension column of every centre of the part (||c'||^2 / 8 as an fp16 pair hi + lo, see estep_ext_kernel), 16 B per centre
-    // behind the ring - formed here from the restarts' norms (no launch per restart) - and the segments' largest norms
-    for (int c = tid; c < nseg * kp; c += 512) {
-        const int sg = c / kp, cc = c - sg * kp;
-        const float v = ((const float*)(a.ws0 + (size_t)slot_of(sg) * a.ws_stride + a.cn_off))[cc];
-        float hv = v * 0.125f;
-        if (!(v < 3.0e38f)) hv = 60000.f;                         // dead centre (padding, NaN): never the best of a row
-        const half_t hi = (half_t)hv;
-        const half_t lo = (half_t)(hv - (float)hi);
-        half8 o;
-#pragma unroll
-        for (int q = 0; q < 8; ++q) o[q] = (half_t)0.f;
-        o[0] = hi;
-        o[1] = lo;
-        *(half8*)(smem + 4 * UB + c * 16) = o;
-    }
-    for (int sg = wave; sg < nseg; sg += 8) {
-        const float* cn = (const float*)(a.ws0 + (size_t)slot_of(sg) * a.ws_stride + a.cn_off);
-        float cm2 = 0.f, wf = 0.f;
-        for (int c = lane; c < kp; c += 64) {
-            const float v = cn[c];
-            if (v < 3.0e38f) cm2 = fmaxf(cm2, v);
-            if (cn_is_wild(v)) wf = 1.f;
-        }
-        cm2 = wave_max_f32(cm2);
-        wf = wave_max_f32(wf);
-        if (lane == 0) cm2s[sg] = wf > 0.f ? -1.f : cm2;           // negative: the segment has a wild centre (prep_center_row)
-    }
-
-    half8 bf[32];
-    const long long row = rblock * 256 + wave * 32 + r;
-    const float xn = xnorm[row < n ? row : n - 1];
-    {
-        const half_t* xr = xh + (row < n ? row : n - 1) * D + 8 * hh;
-#pragma unroll
-        for (int b = 0; b < 4; ++b) {                              // eight fragments at a time (see sim_topk_rb8_kernel)
-#pragma unroll
-            for (int s = 8 * b; s < 8 * b + 8; ++s) bf[s] = *(const half8*)(xr + 16 * s);
-#pragma unroll
-            for (int s = 8 * b; s < 8 * b + 8; ++s) asm volatile("" : "+a"(bf[s]) : : "memory");
-        }
-    }
-    half8 bx;                                                    // B fragment of the extension step: -4 against (hi, lo) = ||c'||^2 / 8, lanes r only
-#pragma unroll
-    for (int q = 0; q < 8; ++q) bx[q] = (half_t)((hh == 0 && q < 2) ? -4.f : 0.f);
-
-    const unsigned bsw = (unsigned)((lane ^ ((4 * wave) & 12)) << 4);
-    const half_t* fbase = nullptr;
-    unsigned fm0 = 0;
-    int f_unit = 0, f_seg = 0, f_in = 0;                         // the unit whose fills are being issued: number, segment, unit inside it
-    auto fill_next = [&]() {                                     // units are filled in order: 0, 1, 2, ...
-        fbase = (const half_t*)(a.ws0 + (size_t)slot_of(f_seg) * a.ws_stride + a.ch_off) + (size_t)f_in * 32 * D;
-        fm0 = sbase + (f_unit & 3) * UB + 4 * wave * 1024;
-        ++f_unit;
-        if (++f_in == upseg) { f_in = 0; ++f_seg; }
-    };
-    auto fill = [&](int p) {
-        const unsigned off = (bsw ^ (unsigned)(p << 4)) + (unsigned)(4 * wave + p) * 1024u;
-        asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2"
-                     ::"s"(fm0 + p * 1024), "v"(off), "s"(fbase) : "memory");
-    };
-    unsigned fa[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) fa[j] = sbase + (unsigned)(r * 1024 + ((32 * j) ^ (16 * (hh ^ (r & 15)))));
-    unsigned fxa = sbase + 4 * UB + (unsigned)(r * 16);          // extension fragment of unit 0, row r (both half-waves read it)
-
-#define ERB_RD(DST, J, IMM) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(DST) : "v"(fa[J]), "n"(IMM))
-#define ERB_RDX(DST) asm volatile("ds_read_b128 %0, %1" : "=v"(DST) : "v"(fxa))
-#define ERB_WAIT(N, FR) asm volatile("s_waitcnt lgkmcnt(" #N ")" : "+v"(FR))
-#define ERB_MFMA(ACC, A, B) asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, %2, %0" : "+v"(ACC) : "v"(A), "a"(B))
-#define ERB_MFMAV(ACC, A, B) asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, %2, %0" : "+v"(ACC) : "v"(A), "v"(B))
-#define ERB_MFMA0(ACC, A, B) asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, %2, 0" : "=&v"(ACC) : "v"(A), "a"(B))
-
-    float b0 = -INFINITY, b1 = -INFINITY, b2 = -INFINITY;        // the lane's three largest keys of the current segment
-    unsigned resv[MAXSEG];                                       // per segment: label | second centre << 8 | state << 16 (1 pair list, 2 all-centres list)
-#pragma unroll
-    for (int i = 0; i < MAXSEG; ++i) resv[i] = 0u;
-    // decision of one finished segment from the half-wave's three best keys: erb_decide's arithmetic, the outcome packed
-    auto decide = [&](int sg) {
-        const float o0 = es_swap32(b0), o1 = es_swap32(b1), o2 = es_swap32(b2);
-        erb_insert(b0, b1, b2, o0);
-        erb_insert(b0, b1, b2, o1);
-        erb_insert(b0, b1, b2, o2);
-        const float m0 = -2.f * b0, m1 = -2.f * b1, m2 = -2.f * b2;
-        // (a segment holds at most 256 centres: EIGHT index bits in a key, i.e. a relative perturbation below 2^-15 of the score where
-        // estep_rb_kernel's eleven bits cost 2^-12 - the key terms of the bound shrink by 8 and with them the rows sent to the refine)
-        const unsigned j0 = __float_as_uint(b0) & 255u, j1 = __float_as_uint(b1) & 255u;
-        const bool wild = cm2s[sg] < 0.f;
-        const float cmax = sqrtf(fmaxf(cm2s[sg], 0.f)) * 1.0000002f;
-        const float sq = 22.627417f;                             // sqrt(512)
-        const float A = 1.5f * (2.02f * (9.765625e-4f + D * 5.9604645e-8f) * cmax + 4.8e-7f * cmax + 6.0e-8f * sq + 6.2e-5f * cmax);
-        const float B = 1.5f * (6.0e-8f * sq * cmax + 4.8e-7f * cmax * cmax + 3.1e-5f * cmax * cmax);
-        const float E = A * xn + B;
-        unsigned state = 0u;
-        if (!(m1 - m0 > 2.0f * E)) state = (m2 - m0 > 2.0f * E) ? 1u : 2u;     // also catches NaN
-        if (wild) state = 2u;
-        const unsigned packed = j0 | (j1 << 8) | (state << 16);
-#pragma unroll
-        for (int i = 0; i < MAXSEG; ++i) resv[i] = (i == sg) ? packed : resv[i];
-        b0 = -INFINITY; b1 = -INFINITY; b2 = -INFINITY;
-    };
-    f32x16 acc[2];
-    half8 fr[4], fx;
-    using yes = std::true_type;
-    using no = std::false_type;
-    using P0 = std::integral_constant<int, 0>;
-    using P1 = std::integral_constant<int, 1>;
-    int e_in = 0, e_seg = 0;                                      // unit u - 1 (the one whose keys are inserted): unit inside its segment, segment
-    auto body = [&](auto has_prev, auto parity, int u) {
-        constexpr int P = decltype(parity)::value;
-        constexpr bool EPI = decltype(has_prev)::value;
-        if (u + 2 < nunits) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-        const bool more = u + 1 < nunits;
-        const bool fills = u + 3 < nunits;
-        if (fills) fill_next();
-        const unsigned ub = (unsigned)(e_in * 32 + 4 * hh);      // centre index (inside its segment) of value i of unit u - 1: ub + (i & 3) + 8 (i >> 2)
-        static_for<0, 32>([&](auto sc) {
-            constexpr int s = decltype(sc)::value;
-            if (s == 29) {
-                const unsigned delta = ((u + 1) & 3) ? (unsigned)UB : (unsigned)(-3 * UB);      // wave-uniform
-#pragma unroll
-                for (int j = 0; j < 8; ++j) fa[j] += delta;
-            }
-            if constexpr (s < 29) ERB_RD(fr[(s + 3) & 3], (s + 3) & 7, ((s + 3) >> 3) * 256);
-            else if (more) ERB_RD(fr[(s + 3) & 3], (s + 3 - 32) & 7, 0);
-            if constexpr (s == 8) ERB_RDX(fx);
-            if constexpr (s >= 8 && s <= 10) ERB_WAIT(3, fr[(s + 1) & 3]);
-            else if (s < 29 || more) ERB_WAIT(2, fr[(s + 1) & 3]);
-            else if (s == 29) ERB_WAIT(1, fr[(s + 1) & 3]);
-            else if (s == 30) ERB_WAIT(0, fr[(s + 1) & 3]);
-            if (s == 0) ERB_MFMA0(acc[P], fr[s & 3], bf[s]);
-            else ERB_MFMA(acc[P], fr[s & 3], bf[s]);
-            if constexpr (s == 20) {
-                asm volatile("" : "+v"(fx));
-                ERB_MFMAV(acc[P], fx, bx);
-                fxa += 512;                                      // next unit's 32 extension entries
-            }
-            if ((s & 7) == 7 && fills) fill(s >> 3);
-            if constexpr (EPI && s >= 2 && s < 18) {
-                constexpr int i = s - 2;
-                const unsigned idx = ub + (unsigned)((i & 3) + 8 * (i >> 2));
-                const float k = __uint_as_float((__float_as_uint(acc[1 - P][i]) & 0xffffff00u) | idx);
-                erb_insert(b0, b1, b2, k);
-            }
-            if constexpr (EPI && s == 22) {                      // unit u - 1 closed its segment: decide it (wave-uniform branch)
-                if (e_in + 1 == upseg) decide(e_seg);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-        });
-        if (EPI) { if (++e_in == upseg) { e_in = 0; ++e_seg; } }
-    };
-#pragma unroll 1
-    for (int pre = 0; pre < 3; ++pre)
-        if (pre < nunits) {
-            fill_next();
-#pragma unroll
-            for (int p = 0; p < 4; ++p) fill(p);
-        }
-    if (nunits > 2) asm volatile("s_waitcnt vmcnt(8) lgkmcnt(0)" ::: "memory");
-    else if (nunits > 1) asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();                                // unit 0, the extension table and the segments' norms are in LDS
-    asm volatile("" ::: "memory");
-    ERB_RD(fr[0], 0, 0);
-    ERB_RD(fr[1], 1, 0);
-    ERB_RD(fr[2], 2, 0);
-    ERB_WAIT(2, fr[0]);
-
-    body(no{}, P0{}, 0);
-    int u = 1;
-    for (; u + 1 < nunits; u += 2) {
-        body(yes{}, P1{}, u);
-        body(yes{}, P0{}, u + 1);
-    }
-    const bool odd_tail = u < nunits;
-    if (odd_tail) body(yes{}, P1{}, u);
-    {   // keys of the last unit (the last of the last segment), then that segment's decision
-        asm volatile("s_nop 15\n\ts_nop 7" : "+v"(acc[0]), "+v"(acc[1]));
-        const unsigned ub = (unsigned)((upseg - 1) * 32 + 4 * hh);
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-            const float av = odd_tail ? acc[1][i] : acc[0][i];
-            erb_insert(b0, b1, b2, __uint_as_float((__float_as_uint(av) & 0xffffff00u) | (ub + (unsigned)((i & 3) + 8 * (i >> 2)))));
-        }
-        decide(nseg - 1);
-    }
-    if (hh != 0 || row >= n) return;
-    // the stream has drained: labels and list entries of every segment
-#pragma unroll
-    for (int sg = 0; sg < MAXSEG; ++sg) {
-        if (sg >= nseg) break;
-        char* wsb = a.ws0 + (size_t)slot_of(sg) * a.ws_stride;
-        const unsigned pk = resv[sg];
-        const int j0 = (int)(pk & 255u), j1 = (int)((pk >> 8) & 255u), state = (int)(pk >> 16);
-        (a.lab0 + (size_t)slot_of(sg) * a.lab_stride)[row] = j0;
-        EHdr* eh = (EHdr*)wsb;
-        if (state == 1) {
-            const int pos = atomicAdd(&eh->flag_cnt, 1);
-            ((int*)(wsb + a.flags_off))[pos] = (int)row;
-            ((int*)(wsb + a.fcand_off))[pos] = j0 | (j1 << 16);
-        } else if (state == 2) {
-            ((int*)(wsb + a.fulls_off))[atomicAdd(&eh->full_cnt, 1)] = (int)row;
-        }
-    }
-#undef ERB_RD
-#undef ERB_RDX
-#undef ERB_WAIT
-#undef ERB_MFMA
-#undef ERB_MFMAV
-#undef ERB_MFMA0
-}
-
 __global__ void __launch_bounds__(256) estep_rb_merge_kernel(const float* __restrict__ tkeys, int nsplit, long long row0, long long n,
                                                              const float* __restrict__ xnorm, const float* __restrict__ cn, int kp,
                                                              EHdr* eh, int* flag_list, int* flag_cand, int* full_list,
@@ -1604,22 +1393,6 @@ __global__ void __launch_bounds__(512) estep_refine_both_kernel(const float* __r
                                                                 int32_t* labels, int32_t* refine_rows_out, int pair_blocks) {
     refine_both_body(X, C, ct, eh, flag_list, flag_cand, full_list, d, k, kp, labels, refine_rows_out, pair_blocks, (int)blockIdx.x, (int)gridDim.x);
 }
-// the same refine for SEVERAL restarts in one launch (behind estep_rbm_kernel): blockIdx.y = the a-th running restart, whose centres,
-// workspace and label slot are strided like the filter's (RbmArgs); the latency-bound chain of an all-centres row is then paid once per
-// iteration, not once per restart
-struct RefmArgs {
-    const float* C0; size_t c_stride;              // centres of slot s: C0 + s * c_stride (floats)
-    char* ws0; size_t ws_stride; size_t ct_off, flags_off, fcand_off, fulls_off;
-    int32_t* lab0; size_t lab_stride;
-    unsigned long long segmap;
-};
-__global__ void __launch_bounds__(512) estep_refine_multi_kernel(const float* __restrict__ X, const RefmArgs a, int d, int k, int kp, int pair_blocks) {
-    const int slot = (int)((a.segmap >> (4 * blockIdx.y)) & 15ull);
-    char* w = a.ws0 + (size_t)slot * a.ws_stride;
-    refine_both_body(X, a.C0 + (size_t)slot * a.c_stride, (const float*)(w + a.ct_off), (const EHdr*)w, (const int*)(w + a.flags_off),
-                     (const int*)(w + a.fcand_off), (const int*)(w + a.fulls_off), d, k, kp, a.lab0 + (size_t)slot * a.lab_stride, nullptr,
-                     pair_blocks, (int)blockIdx.x, (int)gridDim.x);
-}
 
 __global__ void refine_count_kernel(const EHdr* eh, int32_t* out) { *out = eh->flag_cnt + eh->full_cnt; }
 
@@ -1640,27 +1413,18 @@ extern "C" int scd_kmeans_estep(scd_handle h, const float* X, const void* prep, 
     h->prep_ok = 0;
     h->prep_C = nullptr;
     const int dp = dpad(d), kp = kpad(k);
-    char* w = (char*)ws;
-    EHdr* eh = (EHdr*)w;
-    float* cn = (float*)(w + 64);
-    half_t* ch = (half_t*)(w + 64 + scd_align(4 * (size_t)kp));
-    float* ct = (float*)((char*)ch + scd_align(2 * (size_t)kp * dp));
-    int* flags = (int*)((char*)ct + scd_align(4 * (size_t)kp * dp));
-    int* fcand = (int*)((char*)flags + scd_align(4 * (size_t)n));
-    int* fulls = (int*)((char*)fcand + scd_align(4 * (size_t)n));
-    half_t* chf = (half_t*)((char*)fulls + scd_align(4 * (size_t)n));       // centres in MFMA-fragment order (streaming path)
-    float* tkey = (float*)((char*)chf + scd_align(2 * (size_t)kp * dp));    // [3][n] keys / centres between the passes of K > 128
-    int* tidx = (int*)((char*)tkey + scd_align(12 * (size_t)n));
-    const char* p = (const char*)prep;
-    const PrepHdr* ph = (const PrepHdr*)p;
-    const size_t xnorm_off = scd_align(64 + 8 * (size_t)dp);
-    const size_t xh_off = xnorm_off + scd_align(4 * (size_t)n);
-    static const int use_stream = getenv("SCD_ESTEP_STREAM") ? atoi(getenv("SCD_ESTEP_STREAM")) : 1;
-    static const int use_rb = getenv("SCD_ESTEP_RB") ? atoi(getenv("SCD_ESTEP_RB")) : 1;
-    if (use_stream && use_rb && dp == 512 && kp > 128 && kp <= 2048) {
+    const EstepWs w = estep_ws_layout(ws, n, dp, kp);
+    EHdr* eh = w.eh;
+    float *cn = w.cn, *ct = w.ct, *tkey = w.tkey;
+    half_t *ch = w.ch, *chf = w.chf;
+    int *flags = w.flags, *fcand = w.fcand, *fulls = w.fulls, *tidx = w.tidx;
+    const PrepLayout pl = prep_layout(prep, n, dp);
+    const PrepHdr* ph = pl.hdr;
+    const EstepPath path = estep_path(dp, kp);
+    if (path == ESTEP_RB) {
         // single-pass filter (128 < K <= 2048 at Dp = 512): the rows of a block stay in registers, the centres stream past them once
         if (!handover) {
-            prep_centers_kernel<<<kp, 256, 0, st>>>(C, k, d, dp, ph, (const double*)(p + 64), eh, cn, ch, ct_inline(ct, dp, kp), kp, 1, nullptr);
+            prep_centers_kernel<<<kp, 256, 0, st>>>(C, k, d, dp, ph, pl.mu, eh, cn, ch, ct_inline(ct, dp, kp), kp, 1, nullptr);
             if (ct_after(dp, kp)) ct_transpose_kernel<<<dim3(kp / 32, dp / 32), 256, 0, st>>>(C, k, d, dp, kp, ct);
         }
         half_t* ext = chf;                                       // the fragment-order copy is not used on this path: 16 B per centre
@@ -1682,12 +1446,12 @@ extern "C" int scd_kmeans_estep(scd_handle h, const float* X, const void* prep, 
         }
         const int nfull = nsplit > 1 ? (int)(nblk - rem) : (int)nblk;
         float* tk = tkey;                                        // [nsplit][3][tail rows] <= 12 n floats
-        estep_rb_kernel<<<(unsigned)(nfull + (nblk - nfull) * nsplit), 512, ERB_LDS, st>>>((const half_t*)(p + xh_off), (const float*)(p + xnorm_off), ch,
+        estep_rb_kernel<<<(unsigned)(nfull + (nblk - nfull) * nsplit), 512, ERB_LDS, st>>>(pl.xh, pl.xnorm, ch,
                                                                                              ext, cn, eh, flags, fcand, fulls, n, kp, labels_out,
                                                                                              nfull, nsplit, tk);
         if (nsplit > 1)
             estep_rb_merge_kernel<<<(unsigned)scd_cdiv(n - (long long)nfull * 256, 256), 256, 0, st>>>(tk, nsplit, (long long)nfull * 256, n,
-                                                                                                        (const float*)(p + xnorm_off), cn, kp, eh,
+                                                                                                        pl.xnorm, cn, kp, eh,
                                                                                                         flags, fcand, fulls, labels_out);
         if (h->km_timing) {
             SCD_HIP(hipEventRecord(ev1, st));
@@ -1698,19 +1462,19 @@ extern "C" int scd_kmeans_estep(scd_handle h, const float* X, const void* prep, 
         SCD_LAUNCH_CHECK();
         return SCD_OK;
     }
-    if (use_stream && kp <= 2048 && dp <= 768) {
+    if (path == ESTEP_STREAM) {
         // streaming filter (D <= 768): centre prep (unless scd_kmeans_finalize has just produced these very centres and their
         // operands into this workspace), one filter launch per 128 centres, refine; no memset
         const bool prepared = handover;
         if (!prepared) {
-            prep_centers_kernel<<<kp, 256, 0, st>>>(C, k, d, dp, ph, (const double*)(p + 64), eh, cn, ch, ct_inline(ct, dp, kp), kp, 1, chf);
+            prep_centers_kernel<<<kp, 256, 0, st>>>(C, k, d, dp, ph, pl.mu, eh, cn, ch, ct_inline(ct, dp, kp), kp, 1, chf);
             if (ct_after(dp, kp)) ct_transpose_kernel<<<dim3(kp / 32, dp / 32), 256, 0, st>>>(C, k, d, dp, kp, ct);
         }
         const long long g32 = (n + 31) / 32;               // units of 32 rows
         long long grid = g32 < h->n_cu ? g32 : h->n_cu;
         if (grid < scd_cdiv(g32, ES_RMAX / 32)) grid = scd_cdiv(g32, ES_RMAX / 32);
-        const half_t* xh = (const half_t*)(p + xh_off);
-        const float* xn = (const float*)(p + xnorm_off);
+        const half_t* xh = pl.xh;
+        const float* xn = pl.xnorm;
         // refine in the stream kernel's tail only when the caller expects few flagged rows (scd_kmeans_estep_hint: Lloyd iterations
         // after the first two): with ~10 % of the rows flagged the one-block-per-CU tail takes 190 us where the refine kernel at
         // full occupancy takes 60-100; with none flagged the tail saves the launch (37 -> 31 us per call)
@@ -1749,9 +1513,9 @@ extern "C" int scd_kmeans_estep(scd_handle h, const float* X, const void* prep, 
     }
     SCD_HIP(hipMemsetAsync(eh, 0, 64, st));
     // (legacy path: Kp > 2048 or Dp > 768 - estep_refine_full_kernel below reads the transposed copy)
-    prep_centers_kernel<<<kp, 256, 0, st>>>(C, k, d, dp, ph, (const double*)(p + 64), eh, cn, ch, ct_separate(kp) ? nullptr : ct, kp, 0, nullptr);
+    prep_centers_kernel<<<kp, 256, 0, st>>>(C, k, d, dp, ph, pl.mu, eh, cn, ch, ct_separate(kp) ? nullptr : ct, kp, 0, nullptr);
     if (ct_separate(kp)) ct_transpose_kernel<<<dim3(kp / 32, dp / 32), 256, 0, st>>>(C, k, d, dp, kp, ct);
-    estep_mfma_kernel<<<(unsigned)scd_cdiv(n, 128), 256, 0, st>>>((const half_t*)(p + xh_off), (const float*)(p + xnorm_off),
+    estep_mfma_kernel<<<(unsigned)scd_cdiv(n, 128), 256, 0, st>>>(pl.xh, pl.xnorm,
                                                                     ch, cn, eh, flags, fcand, fulls, n, dp, kp, labels_out);
     estep_refine_kernel<<<2048, 64, 0, st>>>(X, C, eh, flags, fcand, d, k, labels_out);
     estep_refine_full_kernel<<<2048, 128, (size_t)d * 8 + 64, st>>>(X, ct, eh, fulls, d, k, kp, labels_out);
@@ -2101,27 +1865,22 @@ static int finalize_impl(scd_handle h, const double* sums, const int64_t* counts
     SCD_REQUIRE(C_old != C_out, "scd_kmeans_finalize: C_out must not alias C_old");
     SCD_REQUIRE(k <= 32768, "scd_kmeans_finalize: k=%d > 32768", k);
     const int dp = dpad(d), kp = kpad(k);
-    static const int use_stream = getenv("SCD_ESTEP_STREAM") ? atoi(getenv("SCD_ESTEP_STREAM")) : 1;
     static const int fuse_env = getenv("SCD_FINALIZE_PREP") ? atoi(getenv("SCD_FINALIZE_PREP")) : 1;
-    const bool fuse = prep && estep_ws && fuse_env && use_stream && kp <= 2048 && dp <= 768;
+    // fused only where the next scd_kmeans_estep takes the hand-over: on the single-pass and the streaming path
+    const bool fuse = prep && estep_ws && fuse_env && estep_path(dp, kp) != ESTEP_LEGACY;
     h->prep_C = nullptr;
     if (fuse) {
         // the NEXT E-step's centre operands, produced by the blocks that produce the centres (saves the prep launch and its gap)
         SCD_REQUIRE(n > 0 && estep_ws_bytes >= scd_kmeans_estep_ws_bytes(n, d, k), "scd_kmeans_finalize: E-step workspace too small");
-        char* w = (char*)estep_ws;
-        EHdr* eh = (EHdr*)w;
-        float* cn = (float*)(w + 64);
-        half_t* ch = (half_t*)(w + 64 + scd_align(4 * (size_t)kp));
-        float* ct = (float*)((char*)ch + scd_align(2 * (size_t)kp * dp));
-        half_t* chf = (half_t*)((char*)ct + scd_align(4 * (size_t)kp * dp) + 3 * scd_align(4 * (size_t)n));
-        const char* p = (const char*)prep;
+        const EstepWs w = estep_ws_layout(estep_ws, n, dp, kp);
+        const PrepLayout pl = prep_layout(prep, n, dp);
         finalize_kernel<<<kp, 256, 0, (hipStream_t)stream_>>>(sums, (const long long*)counts, k, d, C_old, C_out, shift_out,
                                                               (double*)h->scratch, (unsigned*)((char*)h->scratch + 262144), shift_mode,
-                                                              (const PrepHdr*)p, (const double*)(p + 64), eh, cn, ch, ct_inline(ct, dp, kp), kp,
-                                                              chf_unused(dp, kp) ? nullptr : chf, refined_out,
+                                                              pl.hdr, pl.mu, w.eh, w.cn, w.ch, ct_inline(w.ct, dp, kp), kp,
+                                                              chf_unused(dp, kp) ? nullptr : w.chf, refined_out,
                                                               changed_out, changed_acc, stats5, mirror, seq, sums_lab, (const long long*)counts_lab,
                                                               sumsq4, inertia_out);
-        if (ct_after(dp, kp)) ct_transpose_kernel<<<dim3(kp / 32, dp / 32), 256, 0, (hipStream_t)stream_>>>(C_out, k, d, dp, kp, ct);
+        if (ct_after(dp, kp)) ct_transpose_kernel<<<dim3(kp / 32, dp / 32), 256, 0, (hipStream_t)stream_>>>(C_out, k, d, dp, kp, w.ct);
         h->prep_C = C_out;
         h->prep_ws = estep_ws;
         h->prep_k = k;
@@ -3240,17 +2999,13 @@ __global__ void __launch_bounds__(256) xch_unpack_kernel(const double* counts_f6
 // operands from `fsums` / `fcounts` (the rank's own, or the exchanged ones).
 static int lloyd_step_a(scd_handle h, const float* X_u, const void* prep_u, int64_t n_u, const void* X16_cat, int64_t n_cat, int d, int k,
                         int32_t* labels_cat, int32_t* labels_prev, const float* C_in, double* sums, int64_t* counts, double* stats,
-                        int flags, void* ws_e, size_t ws_e_bytes, void* ws_m, size_t ws_m_bytes, void* stream, double* pack_dst,
-                        bool estep_done = false) {
+                        int flags, void* ws_e, size_t ws_e_bytes, void* ws_m, size_t ws_m_bytes, void* stream, double* pack_dst) {
     SCD_DEVICE_ENTRY(h, "scd_kmeans_lloyd_step_delta");
     const int64_t l_num = n_cat - n_u;
     hipStream_t st = (hipStream_t)stream;
-    int rc = SCD_OK;
-    if (!estep_done) {          // (else: the filter of all restarts ran as one launch, estep_multi_launch, and this restart's refine follows it)
-        rc = scd_kmeans_estep_hint(h, flags & (SCD_ESTEP_FEW | SCD_ESTEP_CENTRES_FROM_FINALIZE));
-        if (!rc) rc = scd_kmeans_estep(h, X_u, prep_u, C_in, n_u, d, k, labels_cat + l_num, nullptr, ws_e, ws_e_bytes, stream);
-        if (rc) return rc;
-    }
+    int rc = scd_kmeans_estep_hint(h, flags & (SCD_ESTEP_FEW | SCD_ESTEP_CENTRES_FROM_FINALIZE));
+    if (!rc) rc = scd_kmeans_estep(h, X_u, prep_u, C_in, n_u, d, k, labels_cat + l_num, nullptr, ws_e, ws_e_bytes, stream);
+    if (rc) return rc;
     // rows whose label changed: accumulated in the handle's scratch (zero between iterations), handed to stats[4] by finalize_kernel
     double* changed_acc = (double*)((char*)h->scratch + 262144 + 40);
     if (flags & SCD_LLOYD_FULL) {
@@ -3328,97 +3083,6 @@ extern "C" int scd_kmeans_lloyd_step_delta(scd_handle h, const float* X_u, const
                                  counts_lab, sumsq4, stats, flags, ws_e, ws_e_bytes, ws_m, ws_m_bytes, stream, nullptr, 0.0);
 }
 
-// The filter launch of scd_kmeans_estep for SEVERAL restarts at once (estep_rbm_kernel; Dp = 512, Kp <= 256 per restart): the centre
-// operands of restart j live in its own E-step workspace ws[j] (written by its finalize launch, or by prep_centers_kernel here when the
-// hand-over does not hold - the same test as scd_kmeans_estep's), the workspaces and the label slots are equally strided.  Per restart the
-// refine launch follows on the restart's own stream.  Returns SCD_OK, or a status; *served = false when the shape is not served.
-struct EstepMultiItem { scd_handle h; const float* C; void* ws; int32_t* labels; int slot; };
-static bool estep_multi_serves(int d, int k, int n_items) {
-    const char* ev = getenv("SCD_ESTEP_MERGED");          // read per fit (a test switches it inside one process)
-    const int en = ev ? atoi(ev) : 0;          // opt-in: at C2 the per-restart filters over four streams are faster (9.7-9.9 against 10.2-10.3 ms per stage, round 5)
-    return en && dpad(d) == 512 && kpad(k) <= 256 && n_items >= 2 && n_items <= 16;
-}
-static int estep_multi_launch(const EstepMultiItem* it, int n_items, const float* X, const void* prep, int64_t n, int d, int k, char* ws0,
-                              size_t ws_stride, int32_t* lab0, size_t lab_stride, const float* C0, size_t c_stride, bool vouch, int n_cu,
-                              hipStream_t st) {
-    const int dp = dpad(d), kp = kpad(k);
-    const char* p = (const char*)prep;
-    const PrepHdr* ph = (const PrepHdr*)p;
-    const size_t xnorm_off = scd_align(64 + 8 * (size_t)dp);
-    const size_t xh_off = xnorm_off + scd_align(4 * (size_t)n);
-    RbmArgs a;
-    a.ws0 = ws0; a.ws_stride = ws_stride;
-    a.cn_off = 64;
-    a.ch_off = 64 + scd_align(4 * (size_t)kp);
-    const size_t ct_off = a.ch_off + scd_align(2 * (size_t)kp * dp);
-    a.flags_off = ct_off + scd_align(4 * (size_t)kp * dp);
-    a.fcand_off = a.flags_off + scd_align(4 * (size_t)n);
-    a.fulls_off = a.fcand_off + scd_align(4 * (size_t)n);
-    const size_t chf_off = a.fulls_off + scd_align(4 * (size_t)n);
-    a.lab0 = lab0; a.lab_stride = lab_stride;
-    a.segmap = 0ull;
-    a.n_active = n_items; a.kp = kp;
-    for (int j = 0; j < n_items; ++j) {
-        scd_handle h = it[j].h;
-        char* w = (char*)it[j].ws;
-        SCD_REQUIRE(w == ws0 + (size_t)it[j].slot * ws_stride && it[j].labels == lab0 + (size_t)it[j].slot * lab_stride && it[j].slot < 16,
-                    "estep_multi_launch: workspaces / label slots are not equally strided");
-        a.segmap |= (unsigned long long)it[j].slot << (4 * j);
-        SCD_REQUIRE(!C0 || it[j].C == C0 + (size_t)it[j].slot * c_stride, "estep_multi_launch: centres are not equally strided");
-        // the finalize hand-over of this restart's handle, consumed exactly as scd_kmeans_estep consumes it (`vouch` = the caller's
-        // SCD_ESTEP_CENTRES_FROM_FINALIZE: these centres ARE the previous step's output)
-        const bool handover = vouch && h->prep_C == it[j].C && h->prep_ws == it[j].ws && h->prep_k == k && h->prep_d == d;
-        h->estep_few = 0;
-        h->prep_ok = 0;
-        h->prep_C = nullptr;
-        if (!handover)
-            prep_centers_kernel<<<kp, 256, 0, st>>>(it[j].C, k, d, dp, ph, (const double*)(p + 64), (EHdr*)w, (float*)(w + a.cn_off), (half_t*)(w + a.ch_off),
-                                                    (float*)(w + ct_off), kp, 1, (half_t*)(w + chf_off));
-    }
-    // parts: whole restarts per part (no merge), at most 8 restarts and 1,920 centres each; the count that minimises rounds x (units + ramp)
-    const long long nblk = scd_cdiv(n, 256);
-    const int upseg = kp / 32, ncu = n_cu > 0 ? n_cu : 256;
-    int best_parts = 0;
-    double best_cost = 0.;
-    for (int np = 1; np <= n_items; ++np) {
-        const int segs = (n_items + np - 1) / np;
-        if (segs > 8 || segs * kp > 1920) continue;
-        const double cost = (double)scd_cdiv(nblk * np, ncu) * (segs * upseg + 3);
-        if (!best_parts || cost < best_cost) { best_parts = np; best_cost = cost; }
-    }
-    SCD_REQUIRE(best_parts > 0, "estep_multi_launch: no part count fits");
-    a.nparts = best_parts;
-    { const int rc_ = scd_set_max_lds((const void*)estep_rbm_kernel, ERB_LDS); if (rc_) return rc_; }
-    estep_rbm_kernel<<<(unsigned)(nblk * best_parts), 512, ERB_LDS, st>>>((const half_t*)(p + xh_off), (const float*)(p + xnorm_off), a, n);
-    if (C0) {
-        // the refine of all running restarts in one launch as well (blockIdx.y = restart), each with the single-restart launch's shape
-        // (768 all-centres + 256 pair blocks: with 192 + 64 the all-centres rows of a late iteration took several rounds of their
-        // ~16-us chain, 137 us per launch where the single-restart launches take 10-20)
-        RefmArgs r;
-        r.C0 = C0; r.c_stride = c_stride;
-        r.ws0 = ws0; r.ws_stride = ws_stride; r.ct_off = ct_off; r.flags_off = a.flags_off; r.fcand_off = a.fcand_off; r.fulls_off = a.fulls_off;
-        r.lab0 = lab0; r.lab_stride = lab_stride; r.segmap = a.segmap;
-        estep_refine_multi_kernel<<<dim3(REFINE_GRID, (unsigned)n_items), 512, (size_t)d * 32 + 64, st>>>(X, r, d, k, kp, REFINE_PAIR);
-    }
-    SCD_LAUNCH_CHECK();
-    return SCD_OK;
-}
-// the refine launch of scd_kmeans_estep for one restart, behind the merged filter
-static int estep_multi_refine(const float* X, const float* C, void* ws, int64_t n, int d, int k, int32_t* labels, hipStream_t st) {
-    const int dp = dpad(d), kp = kpad(k);
-    char* w = (char*)ws;
-    const size_t ch_off = 64 + scd_align(4 * (size_t)kp);
-    const size_t ct_off = ch_off + scd_align(2 * (size_t)kp * dp);
-    const size_t flags_off = ct_off + scd_align(4 * (size_t)kp * dp);
-    const size_t fcand_off = flags_off + scd_align(4 * (size_t)n);
-    const size_t fulls_off = fcand_off + scd_align(4 * (size_t)n);
-    estep_refine_both_kernel<<<REFINE_GRID, 512, (size_t)d * 32 + 64, st>>>(X, C, (const float*)(w + ct_off), (EHdr*)w, (int*)(w + flags_off),
-                                                                            (int*)(w + fcand_off), (int*)(w + fulls_off), d, k, kp, labels, nullptr,
-                                                                            REFINE_PAIR);
-    SCD_LAUNCH_CHECK();
-    return SCD_OK;
-}
-
 // The Lloyd loops of a fit's restarts (the loop of scd_amd/kmeans.py:_lloyd_pipelined, faster_mix_k_means_pytorch.py:187-214, :244-275),
 // ONE restart (scd_kmeans_lloyd_run[_sharded]) or ALL of them in lock-step (scd_kmeans_lloyd_run_multi: the restarts are independent
 // once seeded).  Per restart the host runs one iteration behind the device - iteration i + 1 is enqueued (from iteration i's centres,
@@ -3473,7 +3137,7 @@ static int lr_begin(LloydRestart& r, const LloydShared& S) {
     return SCD_OK;
 }
 // first half of iteration `it`: E-step + M-step (+ pack)
-static int lr_launch_a(LloydRestart& r, const LloydShared& S, int it, double* pack_dst, bool estep_done = false, bool refine_done = false) {
+static int lr_launch_a(LloydRestart& r, const LloydShared& S, int it, double* pack_dst) {
     if (r.best_in_ring && r.best_it % 3 == it % 3) { const int rc0 = lr_save_best(r, S); if (rc0) return rc0; }   // that slot is about to be re-used
     const size_t kd = (size_t)S.k * S.d;
     const float* c_in = it == 0 ? r.C_start : r.C_ring + (size_t)((it - 1) % 3) * kd;
@@ -3495,12 +3159,8 @@ static int lr_launch_a(LloydRestart& r, const LloydShared& S, int it, double* pa
     r.h->run_seq += 1.0;
     r.seq_of[it & 1] = r.h->run_seq;
     SCD_REQUIRE(S.k <= 8192, "scd_kmeans_lloyd_run: k > 8192");
-    if (estep_done && !refine_done) {          // the merged filter has run: this restart's refine, then its M-step
-        const int rc = estep_multi_refine(S.X_u, c_in, r.ws_e, S.n_u, S.d, S.k, r.lab_ring + (size_t)(it % 3) * S.n_cat + (S.n_cat - S.n_u), r.st);
-        if (rc) return rc;
-    }
     return lloyd_step_a(r.h, S.X_u, S.prep_u, S.n_u, S.X16_cat, S.n_cat, S.d, S.k, r.lab_ring + (size_t)(it % 3) * S.n_cat, r.labels_prev, c_in,
-                        r.sums, r.counts, stats, r.flags, r.ws_e, S.ws_e_bytes, r.ws_m, S.ws_m_bytes, (void*)r.st, pack_dst, estep_done);
+                        r.sums, r.counts, stats, r.flags, r.ws_e, S.ws_e_bytes, r.ws_m, S.ws_m_bytes, (void*)r.st, pack_dst);
 }
 // second half: centres, shift, inertia, the next E-step's operands, the statistics to the host
 static int lr_launch_b(LloydRestart& r, const LloydShared& S, int it, const double* fsums, const int64_t* fcounts, bool exchanged) {
@@ -3617,29 +3277,6 @@ static int lloyd_run_multi_impl(std::vector<LloydRestart>& rs, const LloydShared
         const int rc = lr_begin(rs[j], S);
         if (rc) return rc;
     }
-    // one merged filter launch per iteration when the shape is served and the restarts' E-step workspaces and label rings are equally
-    // strided (the Python mirror allocates them as one tensor each)
-    bool merge_ok = R >= 2 && estep_multi_serves(S.d, S.k, R);
-    size_t ws_stride = 0, lab_stride = 0;
-    if (merge_ok) {
-        ws_stride = (size_t)((char*)rs[1].ws_e - (char*)rs[0].ws_e);
-        lab_stride = (size_t)(rs[1].lab_ring - rs[0].lab_ring);
-        merge_ok = (char*)rs[1].ws_e > (char*)rs[0].ws_e && rs[1].lab_ring > rs[0].lab_ring && ws_stride >= S.ws_e_bytes;
-        for (int j = 0; j < R && merge_ok; ++j)
-            merge_ok = (char*)rs[j].ws_e == (char*)rs[0].ws_e + (size_t)j * ws_stride && rs[j].lab_ring == rs[0].lab_ring + (size_t)j * lab_stride;
-    }
-    size_t cs_stride = 0, cr_stride = 0;
-    bool cs_ok = false, cr_ok = false;
-    if (merge_ok) {
-        cs_ok = rs[1].C_start > rs[0].C_start;
-        cr_ok = rs[1].C_ring > rs[0].C_ring;
-        cs_stride = cs_ok ? (size_t)(rs[1].C_start - rs[0].C_start) : 0;
-        cr_stride = cr_ok ? (size_t)(rs[1].C_ring - rs[0].C_ring) : 0;
-        for (int j = 0; j < R; ++j) {
-            cs_ok = cs_ok && rs[j].C_start == rs[0].C_start + (size_t)j * cs_stride;
-            cr_ok = cr_ok && rs[j].C_ring == rs[0].C_ring + (size_t)j * cr_stride;
-        }
-    }
     std::vector<int> act;
     size_t n_act_prev = (size_t)R;
     int n_active = R;
@@ -3658,39 +3295,8 @@ static int lloyd_run_multi_impl(std::vector<LloydRestart>& rs, const LloydShared
             for (int j = 0; j < ns; ++j) SCD_HIP(hipStreamWaitEvent(ls->st[j], ls->ev[R + 1], 0));
         }
         n_act_prev = act.size();
-        bool merged = false, refined = false;
-        if (merge_ok && act.size() >= 2) {
-            // ONE filter launch for every running restart (estep_rbm_kernel): the slots the labels go to are freed first, every
-            // restart's stream is joined (its previous finalize wrote the centre operands), and the restarts' streams continue behind it
-            std::vector<EstepMultiItem> items(act.size());
-            for (size_t a = 0; a < act.size(); ++a) {
-                LloydRestart& r = rs[act[a]];
-                if (r.best_in_ring && r.best_it % 3 == it % 3) { const int rc0 = lr_save_best(r, S); if (rc0) return rc0; }
-                const float* c_in = it == 0 ? r.C_start : r.C_ring + (size_t)((it - 1) % 3) * kd;
-                items[a] = {r.h, c_in, r.ws_e, r.lab_ring + (size_t)(it % 3) * S.n_cat + (S.n_cat - S.n_u), act[a]};
-                if (ls) {
-                    SCD_HIP(hipEventRecord(ls->ev[act[a]], r.st));
-                    SCD_HIP(hipStreamWaitEvent(st, ls->ev[act[a]], 0));
-                }
-            }
-            // the restarts' centres of this iteration: the seedings (it = 0) or slot (it - 1) % 3 of the centre rings - one refine launch for
-            // all of them when they are equally strided too
-            const float* c00 = it == 0 ? rs[0].C_start : rs[0].C_ring + (size_t)((it - 1) % 3) * kd;
-            const size_t c_stride = it == 0 ? cs_stride : cr_stride;
-            const bool c_ok = it == 0 ? cs_ok : cr_ok;
-            const int rc = estep_multi_launch(items.data(), (int)items.size(), S.X_u, S.prep_u, S.n_u, S.d, S.k, (char*)rs[0].ws_e, ws_stride,
-                                              rs[0].lab_ring + (size_t)(it % 3) * S.n_cat + (S.n_cat - S.n_u), lab_stride, c_ok ? c00 : nullptr,
-                                              c_stride, it > 0, rs[0].h->n_cu, st);
-            refined = c_ok;
-            if (rc) return rc;
-            if (ls) {
-                SCD_HIP(hipEventRecord(ls->ev[R + 1], st));
-                for (int j = 0; j < ns; ++j) SCD_HIP(hipStreamWaitEvent(ls->st[j], ls->ev[R + 1], 0));
-            }
-            merged = true;
-        }
         for (size_t a = 0; a < act.size(); ++a) {
-            const int rc = lr_launch_a(rs[act[a]], S, it, xch ? xch->buf + a * per : nullptr, merged, refined);
+            const int rc = lr_launch_a(rs[act[a]], S, it, xch ? xch->buf + a * per : nullptr);
             if (rc) return rc;
         }
         if (xch) {

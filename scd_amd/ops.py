@@ -498,8 +498,7 @@ class LloydBuffers:
                 counts=torch.empty((R, k), dtype=torch.int64, device=dev), stats_ring=torch.zeros((R, 2, 5), dtype=torch.float64, device=dev),
                 ws_m=[_ws(self.nb_m, dev) for _ in range(R)],
                 result=np.zeros((R, 4), dtype=np.float64))
-            # the restarts' E-step workspaces as equal strides of ONE buffer (and the label rings above as one tensor): the library then
-            # serves all running restarts' filters with one launch per iteration (estep_rbm_kernel) where the shape allows
+            # the restarts' E-step workspaces as equal strides of ONE buffer: one allocation per fit instead of R
             stride = (int(self.nb_e) + 255) // 256 * 256
             per["ws_e_all"] = _ws(R * stride, dev)
             per["ws_e"] = [per["ws_e_all"][j * stride:(j + 1) * stride] for j in range(R)]

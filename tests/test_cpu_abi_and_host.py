@@ -49,9 +49,11 @@ def test_default_library_has_no_ablation_switches():
     with the -DSCD_ABLATE build that held them: the library neither reads those variables nor contains the code behind them, and
     the sources carry no trace of that build."""
     blob = open(os.path.join(ROOT, "scd_amd", "lib", "libscd_hip.so"), "rb").read()
-    for name in (b"SCD_GEMM_X", b"SCD_SIM_X", b"SCD_ATTN_X", b"SCD_ESTEP_DBG", b"SCD_ESTEP_REFINE_SPLIT", b"SCD_GEMM_MFMA", b"SCD_GEMM_TILE"):
+    for name in (b"SCD_GEMM_X", b"SCD_SIM_X", b"SCD_ATTN_X", b"SCD_ESTEP_DBG", b"SCD_ESTEP_REFINE_SPLIT", b"SCD_GEMM_MFMA", b"SCD_GEMM_TILE",
+                 b"SCD_ESTEP_MERGED"):
         assert name not in blob, name
-    for kern in (b"gemm_w8_kernel", b"gemm_dma16_kernel", b"sim_topk_w4_kernel", b"sim_topk_rb_kernel"):
+    for kern in (b"gemm_w8_kernel", b"gemm_dma16_kernel", b"sim_topk_w4_kernel", b"sim_topk_rb_kernel", b"estep_rbm_kernel",
+                 b"estep_refine_multi_kernel"):
         assert kern not in blob, kern
     csrc = os.path.join(ROOT, "scd_amd", "csrc")
     assert not os.path.exists(os.path.join(csrc, "ablate"))
@@ -59,6 +61,29 @@ def test_default_library_has_no_ablation_switches():
         for f in fs:
             if f.endswith(".py") or (dp.startswith(csrc) and f.endswith((".hip", ".cpp", ".h"))):
                 assert "SCD_ABLATE" not in open(os.path.join(dp, f)).read(), os.path.join(dp, f)     # covers SCD_ABLATE_ENV
+
+
+def test_kmeans_workspace_sizes_match_their_closed_forms():
+    """scd_kmeans_estep_ws_bytes and scd_kmeans_prep_bytes come from the one layout function each (kmeans.hip: estep_ws_layout, prep_layout): the sizes are
+    the closed forms of the layouts `EHdr | cn | ch | ct | 3 lists | chf | tkey | tidx` and `PrepHdr + mu | xnorm | xh (+ 32 rows)`, each
+    part rounded up to 256 bytes, plus 256."""
+    lib = C.CDLL(os.path.join(ROOT, "scd_amd", "lib", "libscd_hip.so"))
+    lib.scd_kmeans_estep_ws_bytes.restype = C.c_size_t
+    lib.scd_kmeans_estep_ws_bytes.argtypes = [C.c_int64, C.c_int, C.c_int]
+    lib.scd_kmeans_prep_bytes.restype = C.c_size_t
+    lib.scd_kmeans_prep_bytes.argtypes = [C.c_int64, C.c_int]
+
+    def A(x):
+        return (x + 255) // 256 * 256
+
+    for n in (1, 255, 256, 4100, 160146):
+        for d in (1, 64, 448, 512, 768, 2032):
+            dp = (d + 127) // 128 * 128
+            assert lib.scd_kmeans_prep_bytes(n, d) == A(64 + 8 * dp) + A(4 * n) + A(2 * (n + 32) * dp) + 256, (n, d)
+            for k in (1, 128, 129, 1000, 2048, 8192):
+                kp = (k + 127) // 128 * 128
+                want = 64 + A(4 * kp) + 2 * A(2 * kp * dp) + A(4 * kp * dp) + 3 * A(4 * n) + 2 * A(12 * n) + 256
+                assert lib.scd_kmeans_estep_ws_bytes(n, d, k) == want, (n, d, k)
 
 
 def test_product_does_not_import_oracle():

@@ -19,8 +19,8 @@ Refined rows per family, summed over the family's cases: the CPU model's predict
   offset              7    3706     3485     3485
   degenerate         10    3758     1606     1606
   outside_box        12    4838     4838     4838     (a centre outside the filters' range: every row to the exact refine)
-The Lloyd paths (default C loop and merged lock-step E-step, estep_rbm_kernel): test_lloyd_paths_on_ladder_and_long_centres, at
-D = 512, K = 40, R = 4 and at D = 448, K = 130, R = 4 (Dp = 512, Kp = 256: two 128-centre chunks).
+The Lloyd path (the default C loop, all restarts in lock-step): test_lloyd_paths_on_ladder_and_long_centres, at
+D = 512, K = 40, R = 4 and at D = 448, K = 130, R = 4 (Dp = 512, Kp = 256: estep_rb_kernel).
 """
 import numpy as np
 import pytest
@@ -136,13 +136,13 @@ def lloyd_data(n, d, k, far_labelled, scatter=24):
 
 @pytest.mark.parametrize("n,d,k,R,far_labelled,scatter", [(2000, 512, 40, 4, False, 24), (2000, 512, 40, 4, True, 24),
                                                           (2000, 448, 130, 4, False, 200)])
-def test_lloyd_paths_on_ladder_and_long_centres(ops, monkeypatch, n, d, k, R, far_labelled, scatter):
-    """One KMeansEngine fit of a few iterations on ladder + long_centres rows through the default C loop and through the merged lock-step
-    E-step (SCD_ESTEP_MERGED, read per fit; estep_rbm_kernel): labels, centres and inertia equal ko.K_Means.  Means leave the grid, so the
+def test_lloyd_paths_on_ladder_and_long_centres(ops, n, d, k, R, far_labelled, scatter):
+    """One KMeansEngine fit of a few iterations on ladder + long_centres rows through the default C loop (the restarts in lock-step):
+    labels, centres and inertia equal ko.K_Means.  Means leave the grid, so the
     oracle's float64 is order-dependent here: the oracle records the smallest relative margin of all its E-steps, and the test asserts it
-    is far above float64 round-off (D 2^-52 ~ 1e-13).  D = 448, K = 130 is Dp = 512, Kp = 256: estep_rb_kernel / estep_rbm_kernel with
-    two 128-centre chunks.  far_labelled: two labelled classes whose centres lie outside the filters' range -
-    every E-step of that fit sends all rows to the exact refine, in estep_rbm_kernel too."""
+    is far above float64 round-off (D 2^-52 ~ 1e-13).  D = 448, K = 130 is Dp = 512, Kp = 256: estep_rb_kernel (D = 512, K = 40: the
+    streaming filter).  far_labelled: two labelled classes whose centres lie outside the filters' range - every E-step of that fit sends
+    all rows to the exact refine."""
     from scd_amd.kmeans import KMeansEngine
     x, lx, ly = lloyd_data(n, d, k, far_labelled, scatter)
     okm = _MarginOracle(k=k, tolerance=1e-4, max_iterations=4, n_init=R, random_state=6)
@@ -152,17 +152,15 @@ def test_lloyd_paths_on_ladder_and_long_centres(ops, monkeypatch, n, d, k, R, fa
         okm.fit(x)
     print("smallest relative margin of the oracle's E-steps: %.3e" % okm.worst)
     assert okm.worst > 1e-10
-    for mode in ("0", "1"):
-        monkeypatch.setenv("SCD_ESTEP_MERGED", mode)
-        km = KMeansEngine(k=k, tolerance=1e-4, max_iterations=4, n_init=R, random_state=6)
-        if far_labelled:
-            km.fit_mix(dev(x), dev(lx), dev(ly))
-        else:
-            km.fit(dev(x))
-        assert km.stats.get("lockstep_fits", 0) == 1
-        assert np.array_equal(km.labels_.cpu().numpy(), okm.labels_), mode
-        assert np.array_equal(km.cluster_centers_.cpu().numpy(), okm.cluster_centers_, equal_nan=True), mode
-        assert float(km.inertia_) == float(okm.inertia_), mode
+    km = KMeansEngine(k=k, tolerance=1e-4, max_iterations=4, n_init=R, random_state=6)
+    if far_labelled:
+        km.fit_mix(dev(x), dev(lx), dev(ly))
+    else:
+        km.fit(dev(x))
+    assert km.stats.get("lockstep_fits", 0) == 1
+    assert np.array_equal(km.labels_.cpu().numpy(), okm.labels_)
+    assert np.array_equal(km.cluster_centers_.cpu().numpy(), okm.cluster_centers_, equal_nan=True)
+    assert float(km.inertia_) == float(okm.inertia_)
 
 
 def _seed_cases():

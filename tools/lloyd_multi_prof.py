@@ -1,6 +1,6 @@
 """An SSKM fit at the default bench's shape (126,976 x 512 clustered fp16-exact features, K = 100, half of the old classes' rows labelled,
 ten restarts x ten iterations) for a rocprofv3 --kernel-trace --stats pass: which kernels the lock-step Lloyd loops spend their time in.
-    python tools/lloyd_multi_prof.py [fits]      (SCD_ESTEP_MERGED / SCD_LLOYD_STREAMS / SCD_LLOYD_LOCKSTEP select the variant)"""
+    python tools/lloyd_multi_prof.py [fits]      (SCD_LLOYD_STREAMS / SCD_LLOYD_LOCKSTEP select the variant)"""
 import os, sys, time
 import numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
