@@ -549,6 +549,58 @@ int scd_image_batch_plan(const int32_t* wh, int batch, int size, int crop, scd_i
 int scd_image_preprocess(scd_handle h, const uint8_t* pixels, int64_t pixel_bytes, const scd_image_desc* descs, const int32_t* plan,
                          int64_t plan_len, int batch, int crop, const void* lut, void* out, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- baseline JPEG decoding, bit-equal to Pillow's Image.open(f).convert('RGB') (torchvision's pil_loader, main_unsup.py:271-289), so that
+ *      only the compressed bytes cross to the device (docs/design/ingest.md, "Device JPEG decode").
+ * Scope: one SOF0 / SOF1 frame of 8-bit samples, 1 component or 3 (YCbCr by libjpeg's rule; chroma 1x1, luma 1x1, 2x1 or 2x2), one scan
+ *   with all components and every table it names present, downsampled chroma wider than 2 samples.  scd_jpeg_parse reports anything
+ *   else as info->reason != 0 (SCD_JPEG_*); such a file is the caller's to decode with Pillow.
+ * scd_jpeg_parse (host): info of one file; rst_offsets (may be NULL with rst_cap 0) receives the file offsets of the first rst_cap RSTn
+ *   markers of the scan, info->n_restarts counts all of them.  Returns SCD_OK whatever the reason.
+ * scd_jpeg_batch_plan (host): descs[n] and the batch's distinct derived Huffman / quantisation tables for files whose infos have reason 0.
+ *   The caller lays the files out back to back at descs[i].data_off (16-byte aligned, data_bytes in all); out_offs[i] is the byte offset of
+ *   image i's w x h x 3 uint8 RGB (HWC) in the pixel section (scd_image_desc.src_off).  With descs == NULL and tables == NULL only the
+ *   three sizes are reported (ws_bytes: workspace of scd_jpeg_decode).
+ * scd_jpeg_decode (device): data / descs / tables are device copies; writes the RGB of every image whose status comes out 0 and
+ *   status[n] (device int32): SCD_JPEG_E* for a stream the decoder cannot follow, for the range guard (a dequantised coefficient
+ *   above 4096 or a column-pass output above 8192 in magnitude: beyond them libjpeg-turbo's 16-bit lanes could differ; a row-pass
+ *   output outside [-512, 511]: beyond it libjpeg-turbo's C code wraps where its SIMD code saturates) and for a
+ *   descriptor that reaches outside data_bytes / tables_bytes / ws_bytes / pixel_bytes.  Such an image's pixels are not written.
+ *   data, tables and ws 16-byte aligned.  The kernels end on any input.
+ * scd_jpeg_decode_host (host): the same functions on the CPU for one file; SCD_EINVAL when the parser rejects it, else *status_out as
+ *   above and, for status 0, rgb[h][w][3]. */
+enum { SCD_JPEG_OK = 0, SCD_JPEG_NOT_JPEG = 1, SCD_JPEG_TRUNCATED = 2, SCD_JPEG_BAD_MARKER = 3, SCD_JPEG_PROGRESSIVE = 4, SCD_JPEG_ARITHMETIC = 5,
+       SCD_JPEG_SOF = 6, SCD_JPEG_PRECISION = 7, SCD_JPEG_COMPONENTS = 8, SCD_JPEG_SAMPLING = 9, SCD_JPEG_COLOURSPACE = 10,
+       SCD_JPEG_MULTISCAN = 11, SCD_JPEG_MISSING_TABLE = 12, SCD_JPEG_BAD_TABLE = 13, SCD_JPEG_CHROMA_WIDTH = 14, SCD_JPEG_DNL = 15 };
+enum { SCD_JPEG_EHUFF = 1, SCD_JPEG_EINDEX = 2, SCD_JPEG_EEOF = 3, SCD_JPEG_EMARKER = 4, SCD_JPEG_ERANGE = 5, SCD_JPEG_EDESC = 6 };
+typedef struct scd_jpeg_info {
+    int32_t reason;            /* 0: device-decodable; else SCD_JPEG_* (the fields below are then as far as the parser got) */
+    int32_t w, h, ncomp;
+    int32_t hs, vs;            /* luma sampling factors (1, 1 for one component) */
+    int32_t restart_interval;  /* MCUs between RSTn markers, 0: none */
+    int32_t file_len;
+    int32_t scan_off, scan_end;/* the scan's bytes: [scan_off, scan_end), scan_end = the marker that ends it or file_len */
+    int32_t has_eoi;           /* that marker is EOI */
+    int32_t n_restarts;        /* RSTn markers inside the scan */
+    int32_t qt_off[3], qt_prec[3]; /* per component: file offset of its quantisation table's 64 entries, 0 = 8-bit / 1 = 16-bit entries */
+    int32_t dc_off[3], ac_off[3];  /* ... of its DC / AC Huffman table (16 counts, then the symbols) */
+} scd_jpeg_info;
+typedef struct scd_jpeg_desc {
+    int64_t data_off;          /* byte offset of the file in `data` */
+    int64_t out_off;           /* byte offset of its RGB in `pixels` */
+    int64_t plane_off;         /* byte offset of its component planes in the workspace */
+    int32_t data_len, scan_off, scan_end, has_eoi;
+    int32_t w, h, ncomp, hs, vs, restart_interval;
+    int32_t qt[3], dc[3], ac[3];   /* byte offsets of the component's tables in `tables` */
+    int32_t pad_;
+} scd_jpeg_desc;
+int scd_jpeg_parse(const uint8_t* data, int64_t len, scd_jpeg_info* info, int32_t* rst_offsets, int64_t rst_cap);
+int scd_jpeg_batch_plan(const uint8_t* const* files, const scd_jpeg_info* infos, const int64_t* out_offs, int n, scd_jpeg_desc* descs,
+                        uint8_t* tables, int64_t tables_cap, int64_t* tables_bytes, int64_t* data_bytes, int64_t* ws_bytes);
+int scd_jpeg_decode(scd_handle h, const uint8_t* data, int64_t data_bytes, const scd_jpeg_desc* descs, const uint8_t* tables,
+                    int64_t tables_bytes, int n, uint8_t* pixels, int64_t pixel_bytes, int32_t* status, void* ws, size_t ws_bytes,
+                    void* stream);
+int scd_jpeg_decode_host(const uint8_t* data, int64_t len, uint8_t* rgb, int64_t rgb_cap, int32_t* status_out);
+
 #ifdef __cplusplus
 }
 #endif

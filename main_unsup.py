@@ -20,6 +20,8 @@ The two things the reference takes from its dataset objects are passed as files 
                  data_utils.py:12-37) for --extract_feat true straight from image files: one PIL decode per image, CLIP's
                  `preprocess` (:271) on the device bit for bit, both towers fed from it, and the two caches above written
                  (scd_amd/images.py; scd_amd.images.list_image_folder lists an ImageFolder tree and its class_to_idx)
+  --decode       with --image_list: `pil` (default), or `device` = baseline JPEGs decoded on the device to the pixels PIL gives, every
+                 other file and every stream the device decoder rejects through PIL (scd_amd/jpeg.py); the caches are the same
 With --synthetic everything is generated from seeds (no dataset / checkpoint needed).
 """
 import argparse
@@ -73,6 +75,8 @@ def build_parser():
     p.add_argument('--class_names', type=str, default='', help='JSON {original class name: class index} of the data set')
     p.add_argument('--images_pt', type=str, default='', help='preprocessed images for --extract_feat true')
     p.add_argument('--image_list', type=str, default='', help='CSV path,target,labelled of image files for --extract_feat true')
+    p.add_argument('--decode', type=str, default='pil', choices=['pil', 'device'],
+                   help="--image_list: decode with Pillow on the host, or baseline JPEGs on the device (same pixels; other files through Pillow)")
     return p
 
 
@@ -144,7 +148,7 @@ def extract_or_load_all(args, feat_model, clip_model):
     from scd_amd import images as img
     paths, targets, mask_lab = img.read_image_list(args.image_list)
     models = {args.feat_model: feat_model, 'clip': clip_model}
-    out = img.extract_features_from_files(paths, targets, mask_lab, models)
+    out = img.extract_features_from_files(paths, targets, mask_lab, models, decode=args.decode)
     fdir = os.path.join(args.root_dir, 'extracted_features')
     os.makedirs(fdir, exist_ok=True)
     torch.save(out[args.feat_model], os.path.join(fdir, fname))

@@ -173,11 +173,26 @@ SIGNATURES = {
     "scd_image_batch_plan": (_i, [_vp, _i, _i, _i, _vp, _vp, _i64, _vp, _vp, _vp]),
     # h, pixels, pixel_bytes, descs, plan, plan_len, batch, crop, lut, out, ws, ws_bytes, stream
     "scd_image_preprocess": (_i, [_vp, _vp, _i64, _vp, _vp, _i64, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    # data, len, info, rst_offsets, rst_cap
+    "scd_jpeg_parse": (_i, [_vp, _i64, _vp, _vp, _i64]),
+    # files, infos, out_offs, n, descs, tables, tables_cap, tables_bytes, data_bytes, ws_bytes
+    "scd_jpeg_batch_plan": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i64, _vp, _vp, _vp]),
+    # h, data, data_bytes, descs, tables, tables_bytes, n, pixels, pixel_bytes, status, ws, ws_bytes, stream
+    "scd_jpeg_decode": (_i, [_vp, _vp, _i64, _vp, _vp, _i64, _i, _vp, _i64, _vp, _vp, _sz, _vp]),
+    # data, len, rgb, rgb_cap, status_out
+    "scd_jpeg_decode_host": (_i, [_vp, _i64, _vp, _i64, _vp]),
 }
 
 # scd_image_desc (include/scd_hip.h) as a numpy record: 40 bytes
 IMAGE_DESC_FIELDS = [("src_off", "<i8"), ("tmp_off", "<i8"), ("w", "<i4"), ("h", "<i4"), ("plan_x", "<i4"), ("plan_y", "<i4"),
                      ("row0", "<i4"), ("rows", "<i4")]
+
+# scd_jpeg_info / scd_jpeg_desc (include/scd_hip.h) as numpy records: 96 and 104 bytes
+JPEG_INFO_FIELDS = [(k, "<i4") for k in ("reason", "w", "h", "ncomp", "hs", "vs", "restart_interval", "file_len", "scan_off", "scan_end",
+                                          "has_eoi", "n_restarts")] + [(k, "<i4", (3,)) for k in ("qt_off", "qt_prec", "dc_off", "ac_off")]
+JPEG_DESC_FIELDS = [("data_off", "<i8"), ("out_off", "<i8"), ("plane_off", "<i8")] + \
+                   [(k, "<i4") for k in ("data_len", "scan_off", "scan_end", "has_eoi", "w", "h", "ncomp", "hs", "vs", "restart_interval")] + \
+                   [(k, "<i4", (3,)) for k in ("qt", "dc", "ac")] + [("pad_", "<i4")]
 
 _lock = threading.Lock()
 _lib = None

@@ -16,7 +16,7 @@ LIB = os.path.join(LIBDIR, "libscd_hip.so")
 OBJDIR = os.path.join(LIBDIR, "obj")
 
 SOURCES = ["api.cpp", "munkres.cpp", "munkres_sparse.cpp", "transport.cpp", "comm.cpp", "kmeans.hip", "mstep.hip", "sim.hip", "vote.hip", "gemm.hip", "encoder.hip",
-           "image.hip", "metrics.hip", "silhouette.hip", "finch.hip"]
+           "image.hip", "jpeg.hip", "metrics.hip", "silhouette.hip", "finch.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-atomics", "-Wno-unused-result",
          "-fno-gpu-rdc"]
@@ -24,6 +24,7 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-ato
 # v_pk_*_f32 (an anti-lever beside MFMAs, MI355X guide) and spills the packed operands it builds for them inside the ring loop
 # image.hip: its host planner restates Pillow's double-precision coefficient code, so no contraction of multiply-adds into FMAs and
 # no fast-math there
+# jpeg.hip: integer code only; it gets the plain FLAGS (which hold no fast-math switch)
 # kmeans.hip: its double-double helpers (dd_add_d, dd_add_prod) switch contraction off with `#pragma clang fp contract(off)`, which the
 # compiler honours only under its default -ffp-contract=fast-honor-pragmas: never give this file -ffp-contract=fast or fast-math
 EXTRA = {"sim.hip": ["-fno-slp-vectorize"], "image.hip": ["-ffp-contract=off", "-fno-fast-math"]}

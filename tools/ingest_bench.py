@@ -1,5 +1,6 @@
 #!/usr/bin/env python
-"""Image-file ingest, stage by stage (docs/design/ingest.md).  `python tools/ingest_bench.py [--images 2048] [--out FILE.json]`
+"""Image-file ingest, stage by stage (docs/design/ingest.md).
+`python tools/ingest_bench.py [--images 2048] [--decode {pil,device}] [--out FILE.json]`
 
 Writes ImageNet-like JPEGs (500x375 and 375x500, quality 90) to a temporary directory and reports
   decode      PIL decode + convert('RGB') only, images/s at 1, 4, 8 and 16 threads;
@@ -8,7 +9,12 @@ Writes ImageNet-like JPEGs (500x375 and 375x500, quality 90) to a temporary dire
   ingest      files -> CLIP + DINO features through scd_amd.images.extract_features_from_files, images/s;
   host route  the same job the way --images_pt is fed today: per-image PIL Resize + CenterCrop + ToTensor + Normalize on the host
               (same thread count), fp32 batches copied to the device, naming.extract_feature per tower;
-and which stage limits the end-to-end rate.  One JSON document on stdout (and in --out)."""
+and which stage limits the end-to-end rate.  With --decode device the same run adds, under "jpeg",
+  ingest      files -> CLIP + DINO features with decode='device', beside the decode='pil' line above, and whether the features are equal;
+  decode      scd_jpeg_decode of a staged batch of 256 alone, ms (HIP events, median of 10 after 2 warm-ups);
+  host side   read + parse only (what the host threads do with decode='device'), images/s at 1, 4, 8 and 16 threads;
+  fallback    the share of files Pillow decoded after all.
+One JSON document on stdout (and in --out)."""
 import argparse
 import json
 import os
@@ -59,9 +65,75 @@ def host_preprocess(path):
     return t.sub_(torch.as_tensor(CLIP_MEAN).view(-1, 1, 1)).div_(torch.as_tensor(CLIP_STD).view(-1, 1, 1))
 
 
+def jpeg_lines(paths, targets, mask_lab, models, got_pil, pil_rate, dev):
+    """The device JPEG decoder's lines of the document (same process, same files as the decode='pil' ingest line)."""
+    from scd_amd import images, jpeg
+    n = len(paths)
+    out = dict(ingest_pil_images_per_s=pil_rate)
+    images.extract_features_from_files(paths[:512], targets[:512], mask_lab[:512], models, decode="device")          # warm-up
+    torch.cuda.synchronize()
+    stats = {}
+    t = time.perf_counter()
+    got = images.extract_features_from_files(paths, targets, mask_lab, models, decode="device", stats=stats)
+    out["ingest_device_images_per_s"] = round(n / (time.perf_counter() - t), 1)
+    out["same_features_as_pil"] = all(np.array_equal(got[k]["all_feats"], got_pil[k]["all_feats"]) for k in models)
+    out["files"] = stats
+    out["fallback_share"] = round((stats["fallback_parser"] + stats["fallback_status"]) / n, 5)
+
+    # host side alone: read + parse
+    out["read_parse_images_per_s"] = {}
+    for th in (1, 4, 8, 16):
+        m = min(n, 512 * th)
+        with ThreadPoolExecutor(th) as ex:
+            list(ex.map(images.read_for_device, paths[:th]))
+            t = time.perf_counter()
+            list(ex.map(images.read_for_device, paths[:m]))
+            out["read_parse_images_per_s"][str(th)] = round(m / (time.perf_counter() - t), 1)
+
+    # the decoder alone on staged batches of 256 and of 1,024: one wave per image, so a larger batch fills the same time
+    for nb in (256, 1024):
+        if nb > n:
+            continue
+        items = [images.read_for_device(p) for p in paths[:nb]]
+        datas, infos = [it[1] for it in items], np.array([it[2] for it in items], dtype=jpeg.INFO)
+        sizes = [3 * int(i["w"]) * int(i["h"]) for i in infos]
+        offs = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+        descs, tables, db, wb = jpeg.batch_plan(datas, infos, offs[:-1])
+        lay = jpeg.JpegLayout(descs, tables, db, wb)
+        host = np.zeros(lay.total, dtype=np.uint8)
+        jpeg.pack(host, lay, descs, tables, datas)
+        staged = torch.from_numpy(host).to(dev)
+        pixels = torch.zeros(int(offs[-1]), dtype=torch.uint8, device=dev)
+        status = torch.zeros(nb, dtype=torch.int32, device=dev)
+        times = []
+        for rep in range(12):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            jpeg.run(staged, lay, pixels, int(offs[-1]), status=status)
+            e1.record()
+            torch.cuda.synchronize()
+            if rep >= 2:
+                times.append(e0.elapsed_time(e1))
+        out["decode_ms_per_%d_median" % nb] = round(float(np.median(times)), 3)
+        out["decode_ms_per_%d_min_max" % nb] = [round(min(times), 3), round(max(times), 3)]
+        out["decode_images_per_s_at_%d" % nb] = round(nb / float(np.median(times)) * 1000, 1)
+        out["decode_status_nonzero_at_%d" % nb] = int(status.count_nonzero().item())
+        out["bytes_per_%d" % nb] = dict(compressed=int(sum(len(d) for d in datas)), tables=int(tables.nbytes), planes=int(wb), rgb_out=int(offs[-1]))
+        del staged, pixels
+
+    # the same ingest with batches of 1,024, both ways
+    for mode in ("pil", "device"):
+        torch.cuda.synchronize()
+        t = time.perf_counter()
+        images.extract_features_from_files(paths, targets, mask_lab, models, decode=mode, batch_size=1024)
+        out["ingest_%s_images_per_s_batch_1024" % mode] = round(n / (time.perf_counter() - t), 1)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--images", type=int, default=2048)
+    ap.add_argument("--decode", default="pil", choices=["pil", "device"], help="device: also measure the device JPEG decoder")
     ap.add_argument("--out", default="")
     a = ap.parse_args()
     torch.set_num_threads(1)                       # host-route threads are the pool's; no intra-op fan-out on top
@@ -144,6 +216,9 @@ def main():
         ingest_s = time.perf_counter() - t
         res["power"] = ps.stop()
         res["ingest_images_per_s"] = round(a.images / ingest_s, 1)
+
+        if a.decode == "device":
+            res["jpeg"] = jpeg_lines(paths, targets, mask_lab, models, got, res["ingest_images_per_s"], dev)
 
         # today's route: host preprocessing, fp32 H2D, naming.extract_feature per tower
         t = time.perf_counter()
