@@ -336,7 +336,11 @@ int scd_sum_f32(scd_handle h, const float* x, int64_t n, double* out, void* stre
 /* ---- vote histogram: Counter(...).most_common(m) per cluster, main_unsup.py:573-586, main_ptsup.py:636-648.
  * name_idx int64 [n, ld] (first top_k columns used); preds int64 [n]; clusters int64 [n_clusters] (ids to vote for);
  * known int64 [n_known] vocabulary ids to drop (may be NULL).  Output per cluster c: keys_out[c, 0..m) and
- * counts_out[c, 0..m) in most_common order (count desc, first-seen asc), padded with -1 / 0. */
+ * counts_out[c, 0..m) in most_common order (count desc, first-seen asc), padded with -1 / 0.
+ * Limits, from the 64-bit sort keys (cluster slot 16 bits | name 24 bits | position 24 bits, then slot | count 24 bits | position):
+ * n_clusters <= 65,536 and cluster ids in [0, 65,536) - an id of `clusters` outside it gets an all-padding row, a prediction outside
+ * it votes for nothing (the Python wrapper refuses such ids in `clusters`); names in [0, 2^24) - a name outside it is dropped like a
+ * `known` one; n * top_k < 2^24 (refused otherwise), which also bounds every count. */
 size_t scd_vote_hist_ws_bytes(int64_t n, int top_k);
 int scd_vote_hist(scd_handle h, const int64_t* name_idx, int64_t n, int ld, int top_k, const int64_t* preds,
                   const int64_t* clusters, int n_clusters, const int64_t* known, int n_known, int m,
@@ -346,7 +350,10 @@ int scd_vote_hist(scd_handle h, const int64_t* name_idx, int64_t n, int ld, int 
  * (row_offset + row) * top_k + column at which it occurs; 0x7f7f7f7f7f7f7f7f = never) - slot_of int32 [n_slots] maps a prediction to its
  * table row (-1: not voted on).  The caller all-reduces counts with SUM and first with MIN over the ranks;
  * scd_vote_table_topm then reads most_common(m) of every cluster off the reduced tables, (count desc, first asc) - the order of
- * Counter.most_common on the concatenated rows (main_unsup.py:573-586).  It zeroes the counts it takes. */
+ * Counter.most_common on the concatenated rows (main_unsup.py:573-586).  Limits: scd_vote_table skips names outside [0, v) and
+ * predictions outside [0, n_slots) or with slot -1, and refuses top_k > ld and (row_offset + n) * top_k >= 2^40; scd_vote_table_topm
+ * compares the whole int32 count (up to 2^31 - 1; cells <= 0 are empty) and the whole 64-bit first.  SIDE EFFECT: scd_vote_table_topm
+ * zeroes the counts it takes (the cells it reports) and leaves every other cell and `first` as they are. */
 int scd_vote_table(scd_handle h, const int64_t* name_idx, int64_t n, int ld, int top_k, const int64_t* preds, const int32_t* slot_of,
                    int n_slots, int64_t row_offset, int64_t v, int n_clusters, int32_t* counts, int64_t* first, void* stream);
 int scd_vote_table_topm(scd_handle h, int32_t* counts, const int64_t* first, int n_clusters, int64_t v, int m, int64_t* keys_out,

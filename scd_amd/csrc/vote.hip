@@ -159,38 +159,51 @@ __global__ void __launch_bounds__(256) vote_table_kernel(const long long* __rest
     atomicMin(&first[(size_t)slot * v + name], (unsigned long long)((row_offset + i) * top_k + j));
 }
 
-// one block per cluster: m rounds of a block-wide arg-max over key = count << 40 | (2^40 - 1 - first); a taken name's count is zeroed
+// most_common order on (count, first-seen, name) as three separate fields: the whole int32 count and the whole 64-bit position take part
+// (packed into one 64-bit key the count had 24 bits, and an all-reduced count of 2^24 ranked as 0).  The name decides only between cells
+// of equal count AND equal position, which a table of scd_vote_table never holds: it makes the result independent of the reduction order.
+__device__ __forceinline__ bool vote_before(int c, unsigned long long f, long long nm, int c2, unsigned long long f2, long long nm2) {
+    if (c != c2) return c > c2;
+    if (f != f2) return f < f2;
+    return nm < nm2;
+}
+
+// one block per cluster: m rounds of a block-wide arg-max in most_common order (count desc, first asc); a taken name's count is zeroed.
+// "Nothing left" is (0, all ones, -1): every cell with a count > 0 comes before it, and two of them never replace each other.
 __global__ void __launch_bounds__(256) vote_table_topm_kernel(int* __restrict__ counts, const unsigned long long* __restrict__ first, long long v,
                                                               int m, long long* __restrict__ keys_out, int* __restrict__ counts_out) {
-    __shared__ unsigned long long rk[4];
+    __shared__ int rc[4];
+    __shared__ unsigned long long rf[4];
     __shared__ long long rn[4];
     const int slot = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     int* cnt = counts + (size_t)slot * v;
     const unsigned long long* fs = first + (size_t)slot * v;
     for (int out = 0; out < m; ++out) {
-        unsigned long long bk = 0;
+        int bc = 0;
+        unsigned long long bf = ~0ull;
         long long bn = -1;
         for (long long nm = threadIdx.x; nm < v; nm += 256) {
             const int c = cnt[nm];
             if (c > 0) {
-                const unsigned long long key = ((unsigned long long)c << 40) | ((1ull << 40) - 1 - (fs[nm] & ((1ull << 40) - 1)));
-                if (key > bk) { bk = key; bn = nm; }
+                const unsigned long long f = fs[nm];
+                if (vote_before(c, f, nm, bc, bf, bn)) { bc = c; bf = f; bn = nm; }
             }
         }
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) {
-            const unsigned long long ok = __shfl_xor(bk, o, 64);
+            const int oc = __shfl_xor(bc, o, 64);
+            const unsigned long long of = __shfl_xor(bf, o, 64);
             const long long on = __shfl_xor(bn, o, 64);
-            if (ok > bk) { bk = ok; bn = on; }
+            if (vote_before(oc, of, on, bc, bf, bn)) { bc = oc; bf = of; bn = on; }
         }
-        if (lane == 0) { rk[wave] = bk; rn[wave] = bn; }
+        if (lane == 0) { rc[wave] = bc; rf[wave] = bf; rn[wave] = bn; }
         __syncthreads();
         if (threadIdx.x == 0) {
             int w = 0;
             for (int q = 1; q < 4; ++q)
-                if (rk[q] > rk[w]) w = q;
+                if (vote_before(rc[q], rf[q], rn[q], rc[w], rf[w], rn[w])) w = q;
             keys_out[(long long)slot * m + out] = rn[w];
-            counts_out[(long long)slot * m + out] = rn[w] >= 0 ? (int)(rk[w] >> 40) : 0;
+            counts_out[(long long)slot * m + out] = rc[w];
             if (rn[w] >= 0) cnt[rn[w]] = 0;
         }
         __syncthreads();

@@ -769,13 +769,22 @@ def sum_f32(x):
 
 
 # ----------------------------------------------------------------------------- vote
+VOTE_MAX_CLUSTER_ID = 65536         # scd_vote_hist: the cluster slot is a 16-bit field of its sort keys (vote.hip)
+
+
 def vote_hist(name_idx, top_k, preds, clusters, m, known=None):
-    """most_common(m) of every cluster's Counter: (keys int64 [C,m], counts int32 [C,m]); -1/0 padded."""
+    """most_common(m) of every cluster's Counter: (keys int64 [C,m], counts int32 [C,m]); -1/0 padded.
+    Limits (the fields of the 64-bit sort keys, scd_vote_hist): cluster ids in [0, 65536) - any other id in `clusters` is refused here,
+    a prediction outside it votes for nothing; names in [0, 2^24) - any other name is dropped like a `known` one; n * top_k < 2^24."""
     _need_cuda(name_idx, preds)
     name_idx = name_idx.to(torch.int64).contiguous()
     preds = preds.to(torch.int64).contiguous()
     dev = name_idx.device
-    clusters = torch.as_tensor(clusters, dtype=torch.int64, device=dev).contiguous()
+    clusters = torch.as_tensor(clusters, dtype=torch.int64).contiguous()
+    if clusters.numel() and (int(clusters.min()) < 0 or int(clusters.max()) >= VOTE_MAX_CLUSTER_ID):
+        raise _lib.ScdError(_lib.SCD_EINVAL, "vote_hist: cluster ids must lie in [0, %d) (got %d .. %d)"
+                            % (VOTE_MAX_CLUSTER_ID, int(clusters.min()), int(clusters.max())))
+    clusters = clusters.to(dev)
     kn = None if known is None or len(known) == 0 else torch.as_tensor(known, dtype=torch.int64, device=dev).contiguous()
     n, ld = name_idx.shape
     nc = clusters.numel()
@@ -790,7 +799,9 @@ def vote_hist(name_idx, top_k, preds, clusters, m, known=None):
 
 def vote_table(name_idx, top_k, preds, clusters, n_slots, row_offset, v):
     """This rank's dense vote tables for its row shard (scd_vote_table): counts int32 [C, V], first int64 [C, V]
-    (global first-seen position, all ones = never).  clusters: the cluster ids voted on, in table-row order."""
+    (global first-seen position (row_offset + row) * top_k + column, 0x7f7f7f7f7f7f7f7f = never).  clusters: the cluster ids voted on,
+    in table-row order.  Names outside [0, v) and predictions outside [0, n_slots) or not in `clusters` are skipped;
+    top_k <= name_idx.shape[1] and (row_offset + n) * top_k < 2^40, or the call is refused."""
     _need_cuda(name_idx, preds)
     name_idx = name_idx.to(torch.int64).contiguous()
     preds = preds.to(torch.int64).contiguous()
@@ -802,13 +813,15 @@ def vote_table(name_idx, top_k, preds, clusters, n_slots, row_offset, v):
     counts = torch.empty((nc, v), dtype=torch.int32, device=dev)
     first = torch.empty((nc, v), dtype=torch.int64, device=dev)
     n, ld = name_idx.shape                  # n == 0 (a shard without unlabelled rows) gives empty tables
-    check(_L().scd_vote_table(handle(), ptr(name_idx), n, max(ld, top_k), top_k, ptr(preds), ptr(slot), n_slots, int(row_offset), int(v), nc,
+    check(_L().scd_vote_table(handle(), ptr(name_idx), n, ld, top_k, ptr(preds), ptr(slot), n_slots, int(row_offset), int(v), nc,
                               ptr(counts), ptr(first), stream_ptr()))
     return counts, first
 
 
 def vote_table_topm(counts, first, m):
-    """most_common(m) per cluster from the (all-reduced) tables: (keys int64 [C, m], counts int32 [C, m]); -1 / 0 padded."""
+    """most_common(m) per cluster from the (all-reduced) tables: (keys int64 [C, m], counts int32 [C, m]); -1 / 0 padded.
+    Order: count descending (any int32 count, up to 2^31 - 1), then `first` ascending (all 64 bits).  SIDE EFFECT: the cells it
+    takes are set to 0 in `counts`; every other cell and `first` stay as they are - pass a clone to keep the table."""
     _need_cuda(counts, first)
     nc, v = counts.shape
     keys = torch.empty((nc, m), dtype=torch.int64, device=counts.device)
