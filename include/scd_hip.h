@@ -462,18 +462,24 @@ int scd_allreduce_centroids(scd_handle h, double* packed, int64_t count, void* s
 int scd_allgather_text(scd_handle h, const void* w_shard, int64_t shard_elems, void* w_full, void* stream);
 
 /* ---- encoders: CLIP ViT-B/16 visual / text (third-party `clip`, call sites main_unsup.py:127,
- *      clip_lang_util.py:101-102) and DINO ViT-B/16 (gcd/models/vision_transformer.py:135-219) ---- */
+ *      clip_lang_util.py:101-102), DINO ViT-B/16 (gcd/models/vision_transformer.py:135-219) and DINOv2 ViT-B/14 / ViT-L/14 with or
+ *      without register tokens (kind 2 with patch 14; LayerScale, the position table at 16 x 16 and the input normalisation are
+ *      folded into the weights by the loader, docs/design/dinov2.md) ---- */
 typedef struct scd_encoder_desc {
-    int kind;          /* 0 CLIP visual, 1 CLIP text, 2 DINO/GCD ViT */
+    int kind;          /* 0 CLIP visual, 1 CLIP text, 2 DINO/GCD/DINOv2 ViT */
     int width, layers, heads, mlp_dim;
-    int tokens;        /* visual: (image/patch)^2 + 1 = 197 (ViT-B/16) or 257 (ViT-L/14); text: 77 */
+    int tokens;        /* visual: (image/patch)^2 + 1 + registers = 197 (ViT-B/16), 257 (patch 14) or 257 + registers <= 288; text: 77 */
     int patch, image;  /* 16 or 14, 224 (visual) */
     int vocab;         /* 49408 (text) */
     int out_dim;       /* 512 (CLIP ViT-B/16), 768 (CLIP ViT-L/14) or 0 = no projection (DINO) */
     int act;           /* 0 QuickGELU, 1 erf GELU */
     float ln_eps;
+    int registers;     /* kind 2 only: register tokens between the class token and the patches (DINOv2 `_reg`: 4), rows that get no
+                        * position embedding; 0 for every other tower.  registers > 0 adds ONE weight pointer behind the last layer's:
+                        * fp32 [registers][width] */
 } scd_encoder_desc;
-/* weights: array of device pointers in the order documented in DESIGN.md (fp16 matrices, fp32 vectors). */
+/* weights: array of device pointers in the order documented in DESIGN.md (fp16 matrices, fp32 vectors); n_weights is checked exactly:
+ * 9 + 12 * layers, + 1 when registers > 0. */
 int scd_encoder_create(scd_handle h, const scd_encoder_desc* desc, const void* const* weights, int n_weights,
                        scd_encoder** out);
 int scd_encoder_destroy(scd_encoder* e);
@@ -498,7 +504,15 @@ int scd_clip_encode_text_len(scd_handle h, const scd_encoder* e, const int32_t* 
  * t sees keys 0..t.  Served: T <= 96, T = 197, non-causal 192 < T <= 224 and non-causal 256 < T <= 288 (SCD_EINVAL otherwise); the
  * kernel is the one the towers run at that T. */
 int scd_attention_f16(scd_handle h, const void* qkv, int batch, int T, int width, int heads, int causal, void* out, void* stream);
-/* building block exposed for tests: the last block's one-query attention (the CLS / EOT row).  kv fp16 [batch*T][2*width] (K | V),
+/* building block exposed for tests: the visual towers' token assembly, through the launcher the towers call.  patch fp16
+ * [batch * np][width] (np = T - 1 - nreg, the patch GEMM's rows), patch_bias fp32 [width] or NULL, cls fp32 [width], pos fp32 [1 + np][width],
+ * registers fp32 [nreg][width] (NULL when nreg == 0) -> out fp16 [rows_pad][width], rows_pad = batch * T rounded up to 256:
+ *   out[b*T + 0] = cls + pos[0];  out[b*T + t] = registers[t - 1] for 1 <= t <= nreg (no position row);
+ *   out[b*T + t] = (patch[b*np + t - 1 - nreg] + patch_bias) + pos[t - nreg] for t > nreg;  rows >= batch * T are zeros.
+ * stats int64 [rows_pad][2] or NULL: the rows' LayerNorm statistics in scd_gemm_ln's fixed point.  width % 256 == 0, width <= 1024. */
+int scd_vit_assemble_f16(scd_handle h, const void* patch, const float* patch_bias, const float* cls, const float* pos,
+                         const float* registers, int nreg, int batch, int T, int width, void* out, int64_t* stats, void* stream);
+/* building block exposed for tests: the last block's one-query attention (the CLS / EOT row). kv fp16 [batch*T][2*width] (K | V),
  * q and out fp16 [batch][width], T <= 256; qrow int32 [batch] on the device = b*T + the query's position (causal: the last key it
  * sees; may be NULL when causal == 0, then every key is seen). */
 int scd_attention_single_query_f16(scd_handle h, const void* kv, const void* q, const int* qrow, int batch, int T, int width,

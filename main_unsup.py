@@ -53,7 +53,9 @@ def build_parser():
     p.add_argument('--num_workers', default=2, type=int)
     p.add_argument('--root_dir', type=str, default='/Your_data_dir')
     p.add_argument('--dataset_name', type=str, default='imagenet_1000')
-    p.add_argument('--feat_model', type=str, default='dino_vit')
+    p.add_argument('--feat_model', type=str, default='dino_vit',
+                   help='clustering features: clip, dino_vit, gcd, or a DINOv2 tower dinov2_vitb14 | dinov2_vitl14 | dinov2_vitb14_reg | '
+                        'dinov2_vitl14_reg ($SCD_ROOT/dinov2/); the cache files carry the name as given')
     p.add_argument('--prop_train_labels', type=float, default=0.5)
     p.add_argument('--transform', type=str, default='imagenet')
     p.add_argument('--extract_feat', type=str2bool, default=False)
@@ -157,9 +159,12 @@ def extract_or_load_all(args, feat_model, clip_model):
 
 
 def load_feat_model(args, clip_model):
-    """:240-264.  dino_vit / gcd weights come from $SCD_ROOT (no torch.hub offline)."""
+    """:240-264.  dino_vit / gcd / dinov2_* weights come from $SCD_ROOT (no torch.hub offline)."""
     if args.feat_model == 'clip':
         return clip_model
+    if args.feat_model.startswith('dinov2'):
+        # $SCD_ROOT/dinov2/{name}_pretrain.pth; an unknown name is a ValueError, a missing file a FileNotFoundError naming the path
+        return clip.load_dinov2(args.feat_model, root=os.environ.get("SCD_ROOT", args.root_dir)).cuda()
     from scd_amd.clip import DinoViT
     path = os.path.join(os.environ.get("SCD_ROOT", args.root_dir), 'dino' if args.feat_model == 'dino_vit' else 'gcd',
                         f'{args.feat_model}_{args.dataset_name}.pt' if args.feat_model == 'gcd' else 'dino_vitbase16_pretrain.pth')

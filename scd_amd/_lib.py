@@ -24,7 +24,7 @@ class ScdError(RuntimeError):
 class EncoderDesc(C.Structure):
     _fields_ = [("kind", C.c_int), ("width", C.c_int), ("layers", C.c_int), ("heads", C.c_int), ("mlp_dim", C.c_int),
                 ("tokens", C.c_int), ("patch", C.c_int), ("image", C.c_int), ("vocab", C.c_int), ("out_dim", C.c_int),
-                ("act", C.c_int), ("ln_eps", C.c_float)]
+                ("act", C.c_int), ("ln_eps", C.c_float), ("registers", C.c_int)]
 
 
 _vp, _i, _i64, _sz, _f = C.c_void_p, C.c_int, C.c_int64, C.c_size_t, C.c_float
@@ -166,6 +166,7 @@ SIGNATURES = {
     "scd_gemm_img_f16": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _i, _vp]),
     "scd_layernorm_f16": (_i, [_vp, _vp, _vp, _i64, _i, _f, _vp, _vp, _vp, _vp]),
     "scd_attention_f16": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
+    "scd_vit_assemble_f16": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     "scd_attention_single_query_f16": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "scd_image_geometry": (_i, [_i, _i, _i, _i, _vp]),
     "scd_image_plan_axis": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _i64, _vp]),

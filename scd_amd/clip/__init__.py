@@ -99,6 +99,51 @@ def load(name="ViT-B/16", device=None, jit=False, download_root=None, seed=0, sy
     return model, _preprocess(_MODELS[name]["image"])
 
 
+def dinov2_models():
+    return list(weights.DINOV2)
+
+
+def dinov2_checkpoint_path(name, root=None):
+    """$SCD_ROOT/dinov2/{name}_pretrain.pth, upstream's file names: dinov2_vitb14_pretrain.pth, dinov2_vitb14_reg4_pretrain.pth."""
+    if name not in weights.DINOV2:
+        raise ValueError("DINOv2 model %r not found; served: %s (ViT-S/14 and ViT-g/14 are not)" % (name, dinov2_models()))
+    root = root if root is not None else os.environ.get("SCD_ROOT", "")
+    stem = name[:-len("_reg")] + "_reg4" if name.endswith("_reg") else name
+    return os.path.join(root or "$SCD_ROOT", "dinov2", stem + "_pretrain.pth")
+
+
+def load_dinov2(name, root=None, synthetic=False, seed=2, **options):
+    """The DINOv2 feature tower `name` (dinov2_vitb14, dinov2_vitl14, dinov2_vitb14_reg, dinov2_vitl14_reg) at 224 x 224 as a DinoViT:
+    features(x, normalize) -> float32 [B, 768 | 1024] from the CLIP-normalised pixels the ingest path produces.
+
+    Reads the facebookresearch/dinov2 state dict at dinov2_checkpoint_path(name, root); a missing file raises FileNotFoundError naming
+    it unless synthetic=True asks for seeded random-init weights (benchmarks, tests).  options (weights.prepare_dinov2):
+      pos_interp  how pos_embed (37 x 37, trained at 518 px) is resampled to 16 x 16 at load: 'offset' | 'size_antialias' | 'size'.
+                  Default by checkpoint: 'offset' without registers, 'size_antialias' with - upstream's hub settings as recalled
+                  (interpolate_offset=0.1 / interpolate_antialias=False, and 0.0 / True for `_reg`), NOT verified against upstream.
+      input_norm  'imagenet' (default: the ImageNet mean / std DINOv2 was trained with are folded into the patch embedding, so the
+                  CLIP-normalised batch gives the features of the ImageNet-normalised one) | 'clip' (no fold).
+      image       224 only."""
+    path = dinov2_checkpoint_path(name, root)
+    cfg = weights.DINOV2[name]
+    if synthetic:
+        sd = weights.synthetic_dinov2_state_dict(seed=seed, width=cfg["width"], layers=cfg["layers"], registers=cfg["registers"])
+    elif os.path.exists(path):
+        sd = torch.load(path, map_location="cpu", weights_only=False)
+        sd = sd.state_dict() if hasattr(sd, "state_dict") else sd
+    else:
+        raise FileNotFoundError("DINOv2 checkpoint %s not found: put upstream's %s there (or pass root=); seeded random-init weights "
+                                "must be requested explicitly with load_dinov2(..., synthetic=True)" % (path, os.path.basename(path)))
+    model = DinoViT(sd, **options)              # refuses what the towers do not serve (weights.dinov2_check)
+    got = weights.dinov2_check(sd, options.get("image", 224))
+    if (got["width"], got["registers"]) != (cfg["width"], cfg["registers"]):
+        raise ValueError("DINOv2 checkpoint %s holds width %d with %d register tokens, not the %s model (width %d, %d registers)"
+                         % (path, got["width"], got["registers"], name, cfg["width"], cfg["registers"]))
+    model.synthetic = bool(synthetic)
+    model.name = name
+    return model
+
+
 # ----------------------------------------------------------------------------- tokenizer
 class SimpleTokenizer:
     """Byte-level BPE of openai/CLIP simple_tokenizer (lower-cased, SOT 49406, EOT 49407).

@@ -64,18 +64,30 @@ def build_clip_text(sd, dev):
     return ops.Encoder(desc, ws)
 
 
-def build_dino(sd, dev):
+def build_dino(sd, dev, **dinov2_options):
+    """DINO / GCD ViT-B/16, or - recognised by `ls1.gamma` / `register_tokens` keys - a DINOv2 ViT-B/14 / ViT-L/14 state dict, which
+    goes through weights.prepare_dinov2 (dinov2_options: pos_interp, input_norm, image) first.  The register rows are the one weight
+    behind the last layer's (DESIGN.md 'weight order')."""
+    if W.is_dinov2(sd):
+        sd = W.prepare_dinov2(sd, **dinov2_options)
+    elif dinov2_options:
+        raise ValueError("build_dino: %s apply to DINOv2 state dicts only" % sorted(dinov2_options))
     w = sd["patch_embed.proj.weight"]
     width, patch = w.shape[0], w.shape[-1]
-    tokens = sd["pos_embed"].shape[1]
-    image = int(round((tokens - 1) ** 0.5)) * patch
+    pos_rows = sd["pos_embed"].shape[1]
+    registers = sd["register_tokens"].shape[1] if "register_tokens" in sd else 0
+    tokens = pos_rows + registers
+    image = int(round((pos_rows - 1) ** 0.5)) * patch
     layers = _count(sd, "blocks.")
     ws = [_f16(w.reshape(width, -1), dev), _f32(sd["patch_embed.proj.bias"], dev), _f32(sd["cls_token"].reshape(-1), dev),
-          _f32(sd["pos_embed"].reshape(tokens, width), dev), None, None, _f32(sd["norm.weight"], dev),
+          _f32(sd["pos_embed"].reshape(pos_rows, width), dev), None, None, _f32(sd["norm.weight"], dev),
           _f32(sd["norm.bias"], dev), None]
     ws += _pack_layers(sd, "blocks.", W.DINO_BLOCK_KEYS, layers, dev)
     desc = dict(kind=2, width=width, layers=layers, heads=width // 64, mlp_dim=4 * width, tokens=tokens, patch=patch,
                 image=image, vocab=0, out_dim=0, act=1, ln_eps=1e-6)
+    if registers:
+        ws.append(_f32(sd["register_tokens"].reshape(registers, width), dev))
+        desc["registers"] = registers
     return ops.Encoder(desc, ws)
 
 
@@ -144,13 +156,19 @@ class CLIP:
 
 
 class DinoViT:
-    """Callable like the torch.hub dino_vitb16 module the reference uses (main_unsup.py:241,129)."""
+    """Callable like the torch.hub dino_vitb16 module the reference uses (main_unsup.py:241,129).  A DINOv2 state dict
+    (facebookresearch/dinov2 layout) is served too; dinov2_options are weights.prepare_dinov2's (pos_interp, input_norm, image) and are
+    checked here, on the host."""
 
-    def __init__(self, state_dict):
-        self._sd = state_dict
-        self._enc = None
+    def __init__(self, state_dict, **dinov2_options):
+        self._opts = dinov2_options
+        self.load_state_dict(state_dict)
 
     def load_state_dict(self, sd, strict=True):
+        if W.is_dinov2(sd):
+            sd = W.prepare_dinov2(sd, **self._opts)       # raises ValueError for what the towers do not serve
+        elif self._opts:
+            raise ValueError("DinoViT: %s apply to DINOv2 state dicts only" % sorted(self._opts))
         self._sd = sd
         self._enc = None
 

@@ -1,6 +1,8 @@
 // Transformer encoder towers for gfx950: CLIP ViT-B/16 and ViT-L/14 visual and text (third-party `clip`, call sites
 // /root/reference/main_unsup.py:127 and local_utils/clip_lang_util.py:101-102; structure in SURVEY.md appendix B)
-// and the DINO/GCD ViT-B/16 of /root/reference/gcd/models/vision_transformer.py:135-219.
+// and the DINO/GCD ViT-B/16 of /root/reference/gcd/models/vision_transformer.py:135-219.  DINOv2 ViT-B/14 / ViT-L/14 (with or without
+// register tokens) run as kind 2 at patch 14: the register rows are placed by the token assembly, LayerScale / the position table / the
+// input normalisation are folded into the weights by the loader (docs/design/dinov2.md).
 //
 // Data layout: activations are token-major [image*T + token][width] fp16 (the residual stream is fp16 like the
 // reference's `clip.load` model on GPU); LayerNorm statistics, softmax and every GEMM accumulate in fp32.
@@ -31,6 +33,9 @@ struct scd_encoder {
 
 enum { W_PATCH = 0, W_PATCH_B = 1, W_CLS = 2, W_POS = 3, W_LNPRE_W = 4, W_LNPRE_B = 5, W_LNPOST_W = 6, W_LNPOST_B = 7,
        W_PROJ = 8, W_LAYER0 = 9, W_PER_LAYER = 12 };
+// desc.registers > 0 (kind 2): one more pointer BEHIND the last layer's twelve, fp32 [registers][width]; absent otherwise, so the
+// weight lists of the towers without registers are what they were
+static inline int w_registers(const scd_encoder_desc& d) { return W_LAYER0 + W_PER_LAYER * d.layers; }
 enum { L_LN1_W = 0, L_LN1_B, L_QKV_W, L_QKV_B, L_PROJ_W, L_PROJ_B, L_LN2_W, L_LN2_B, L_FC1_W, L_FC1_B, L_FC2_W, L_FC2_B };
 
 // ------------------------------------------------------------------------------------------------ LayerNorm
@@ -165,8 +170,12 @@ __global__ void __launch_bounds__(256) pad_cols_kernel(const half_t* __restrict_
 }
 
 // token assembly (+ optional ln_pre): x[b][0] = cls + pos[0]; x[b][1+p] = patch[b*np+p] + patch_bias + pos[1+p]
+// With nreg register tokens (DINOv2 `_reg` checkpoints; T = 1 + nreg + np): rows 1..nreg are registers[t-1] as they are (no position
+// row is added to a register), and the patch rows move up: x[b][1+nreg+p] = patch[b*np+p] + patch_bias + pos[1+p].  nreg = 0 takes
+// the loads and the fp32 additions it always took.
 __global__ void __launch_bounds__(256) assemble_visual_kernel(const half_t* __restrict__ patch, const float* __restrict__ patch_b,
                                                               const float* __restrict__ cls, const float* __restrict__ pos,
+                                                              const float* __restrict__ registers, int nreg,
                                                               long long rows, int batch, int T, int width, const float* __restrict__ lg,
                                                               const float* __restrict__ lb, float eps, half_t* __restrict__ out,
                                                               long long* __restrict__ stats) {
@@ -185,16 +194,24 @@ __global__ void __launch_bounds__(256) assemble_visual_kernel(const half_t* __re
     }
     float s1 = 0.f, s2 = 0.f;
     float v[4][4];
+    const bool is_reg = t >= 1 && t <= nreg;      // a register row: no position row
+    const int tp = t > nreg ? t - nreg : 0;       // the position row of a class (0) / patch (1 + p) token
+    const int np = T - 1 - nreg;
 #pragma unroll
     for (int i = 0; i < 4; ++i)
         if (i < groups) {
             const int c = (i * 64 + lane) * 4;
-            const float4 pp = *(const float4*)(pos + (size_t)t * width + c);
+            if (is_reg) {
+                const float4 a = *(const float4*)(registers + (size_t)(t - 1) * width + c);
+                v[i][0] = a.x; v[i][1] = a.y; v[i][2] = a.z; v[i][3] = a.w;
+                continue;
+            }
+            const float4 pp = *(const float4*)(pos + (size_t)tp * width + c);
             float4 a;
             if (t == 0) {
                 a = *(const float4*)(cls + c);
             } else {
-                const half4 h4 = *(const half4*)(patch + ((size_t)b * (T - 1) + (t - 1)) * width + c);
+                const half4 h4 = *(const half4*)(patch + ((size_t)b * np + (tp - 1)) * width + c);
                 a = make_float4((float)h4[0], (float)h4[1], (float)h4[2], (float)h4[3]);
                 if (patch_b) {
                     const float4 pb = *(const float4*)(patch_b + c);
@@ -227,6 +244,7 @@ __global__ void __launch_bounds__(256) assemble_visual_kernel(const half_t* __re
 template <int RB>
 __global__ void __launch_bounds__(256) assemble_visual_rows_kernel(const half_t* __restrict__ patch, const float* __restrict__ patch_b,
                                                                    const float* __restrict__ cls, const float* __restrict__ pos,
+                                                                   const float* __restrict__ registers, int nreg,
                                                                    long long rows, int batch, int T, int width, const float* __restrict__ lg,
                                                                    const float* __restrict__ lb, float eps, half_t* __restrict__ out,
                                                                    long long* __restrict__ stats) {
@@ -244,25 +262,33 @@ __global__ void __launch_bounds__(256) assemble_visual_rows_kernel(const half_t*
     }
     const int t = (int)(item % T);
     const int b0 = (int)(item / T) * RB;
+    const bool is_reg = t >= 1 && t <= nreg;      // a register row (the same for the RB images of the item): no position row
+    const int tp = t > nreg ? t - nreg : 0;       // the position row of a class (0) / patch (1 + p) token
+    const int np = T - 1 - nreg;
     float4 pp[4], ca[4], gg[4], bb[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i)
         if (i < groups) {
             const int c = (i * 64 + lane) * 4;
-            pp[i] = *(const float4*)(pos + (size_t)t * width + c);
-            ca[i] = t == 0 ? *(const float4*)(cls + c) : (patch_b ? *(const float4*)(patch_b + c) : make_float4(0.f, 0.f, 0.f, 0.f));
+            if (is_reg) {
+                pp[i] = make_float4(0.f, 0.f, 0.f, 0.f);      // never added
+                ca[i] = *(const float4*)(registers + (size_t)(t - 1) * width + c);
+            } else {
+                pp[i] = *(const float4*)(pos + (size_t)tp * width + c);
+                ca[i] = t == 0 ? *(const float4*)(cls + c) : (patch_b ? *(const float4*)(patch_b + c) : make_float4(0.f, 0.f, 0.f, 0.f));
+            }
             if (lg) { gg[i] = *(const float4*)(lg + c); bb[i] = *(const float4*)(lb + c); }
         }
     // all RB rows' patch values first: 3 x RB loads in flight per wave before the first reduction (one row at a time, a wave had 1.5 KB
     // in flight and the launch ran at the latency of its dependent load -> reduce -> store chains)
     half4 hv[RB][4];
-    if (t != 0) {
+    if (t > nreg) {
 #pragma unroll
         for (int q = 0; q < RB; ++q) {
             const int b = b0 + q < batch ? b0 + q : batch - 1;
 #pragma unroll
             for (int i = 0; i < 4; ++i)
-                if (i < groups) hv[q][i] = *(const half4*)(patch + ((size_t)b * (T - 1) + (t - 1)) * width + (i * 64 + lane) * 4);
+                if (i < groups) hv[q][i] = *(const half4*)(patch + ((size_t)b * np + (tp - 1)) * width + (i * 64 + lane) * 4);
         }
     }
 #pragma unroll
@@ -274,6 +300,10 @@ __global__ void __launch_bounds__(256) assemble_visual_rows_kernel(const half_t*
 #pragma unroll
         for (int i = 0; i < 4; ++i)
             if (i < groups) {
+                if (is_reg) {
+                    v[i][0] = ca[i].x; v[i][1] = ca[i].y; v[i][2] = ca[i].z; v[i][3] = ca[i].w;
+                    continue;
+                }
                 float4 a;
                 if (t == 0) {
                     a = ca[i];
@@ -1023,7 +1053,7 @@ static inline EncPad make_pad(const scd_encoder_desc& d, int batch, int tokens =
     p.tokens = tokens > 0 ? tokens : d.tokens;
     p.bh = (batch + 255) / 256 * 256;
     p.rows = ((long long)batch * p.tokens + 255) / 256 * 256;
-    p.prows = ((long long)batch * (p.tokens - 1) + 255) / 256 * 256;
+    p.prows = ((long long)batch * (p.tokens - 1 - d.registers) + 255) / 256 * 256;
     return p;
 }
 
@@ -1069,8 +1099,10 @@ extern "C" int scd_encoder_create(scd_handle h, const scd_encoder_desc* desc, co
     SCD_REQUIRE(d.width % 256 == 0 && d.width <= 1024 && d.width == d.heads * 64, "scd_encoder_create: width %d / heads %d (head_dim must be 64)", d.width, d.heads);
     SCD_REQUIRE(d.mlp_dim % 128 == 0 && d.layers > 0, "scd_encoder_create: bad mlp_dim/layers");
     SCD_REQUIRE(d.out_dim == 0 || d.out_dim % 128 == 0, "scd_encoder_create: out_dim %d must be a multiple of 128", d.out_dim);
-    SCD_REQUIRE(n_weights == W_LAYER0 + W_PER_LAYER * d.layers, "scd_encoder_create: expected %d weight pointers, got %d",
-                W_LAYER0 + W_PER_LAYER * d.layers, n_weights);
+    SCD_REQUIRE(d.registers >= 0 && (d.registers == 0 || d.kind == 2),
+                "scd_encoder_create: registers = %d: register tokens exist for kind 2 (DINO-style ViT) only, got kind %d", d.registers, d.kind);
+    const int n_expected = W_LAYER0 + W_PER_LAYER * d.layers + (d.registers > 0 ? 1 : 0);
+    SCD_REQUIRE(n_weights == n_expected, "scd_encoder_create: expected %d weight pointers, got %d", n_expected, n_weights);
     if (d.kind == 1) {
         SCD_REQUIRE(d.tokens == 77 && d.vocab > 0, "scd_encoder_create: text tower expects 77 tokens");
         SCD_REQUIRE(weights[W_PATCH] && weights[W_POS] && weights[W_LNPOST_W] && weights[W_LNPOST_B] && weights[W_PROJ] && d.out_dim > 0,
@@ -1079,8 +1111,11 @@ extern "C" int scd_encoder_create(scd_handle h, const scd_encoder_desc* desc, co
         SCD_REQUIRE(d.patch > 0 && d.image % d.patch == 0 && scd_cdiv(3 * d.patch * d.patch, 64) * 64 <= 3 * d.width,
                     "scd_encoder_create: bad patch/image");
         const int np = (d.image / d.patch) * (d.image / d.patch);
-        SCD_REQUIRE(d.tokens == np + 1 && (d.tokens == 197 || d.tokens == 257),
-                    "scd_encoder_create: visual tower expects (image/patch)^2 + 1 = 197 or 257 tokens, got %d", d.tokens);
+        // the token counts the attention ladder serves (launch_attention): 197, or the non-causal 256 < T <= 288 range
+        SCD_REQUIRE(d.tokens == np + 1 + d.registers && (d.tokens == 197 || (d.tokens >= 257 && d.tokens <= 288)),
+                    "scd_encoder_create: visual tower expects (image/patch)^2 + 1 + registers = 197 or 257..288 tokens, got %d "
+                    "(%d patches, %d registers)", d.tokens, np, d.registers);
+        SCD_REQUIRE(d.registers == 0 || weights[w_registers(d)], "scd_encoder_create: registers = %d but the register rows are null", d.registers);
         SCD_REQUIRE(weights[W_PATCH] && weights[W_CLS] && weights[W_POS] && weights[W_LNPOST_W] && weights[W_LNPOST_B],
                     "scd_encoder_create: visual tower weight missing");
         SCD_REQUIRE((d.out_dim > 0) == (weights[W_PROJ] != nullptr), "scd_encoder_create: projection / out_dim mismatch");
@@ -1370,6 +1405,27 @@ static int run_head(const scd_encoder* e, const EncWs& w, const EncPad& pad, boo
     return SCD_OK;
 }
 
+// The token assembly of the visual towers (scd_vit_encode_image) and of scd_vit_assemble_f16: patch GEMM rows + patch bias + class token +
+// position rows (+ register rows) -> the residual stream x [rows][width] and, with stats, the first block's LayerNorm statistics.
+static void launch_assemble(const half_t* patch, const float* patch_b, const float* cls, const float* pos, const float* registers, int nreg,
+                            long long rows, int batch, int T, int width, const float* lg, const float* lb, float eps, half_t* x,
+                            long long* stats, hipStream_t st) {
+    static const int asm_rb = getenv("SCD_ASSEMBLE_ROWS") ? atoi(getenv("SCD_ASSEMBLE_ROWS")) : 4;     // 1: one row per wave (round 1-5 kernel; A/B, same bits); 8: eight
+    if (asm_rb > 1 && width <= 1024) {
+#define ASM_GO(RB)                                                                                                                        \
+    do {                                                                                                                                  \
+        const long long items = (long long)T * ((batch + RB - 1) / RB) + (rows - (long long)batch * T);                                   \
+        assemble_visual_rows_kernel<RB><<<(unsigned)scd_cdiv(items, 4), 256, 0, st>>>(patch, patch_b, cls, pos, registers, nreg, rows, batch, T, \
+                                                                                      width, lg, lb, eps, x, stats);                      \
+    } while (0)
+        if (asm_rb == 8) ASM_GO(8); else ASM_GO(4);       // measured (tools/asm_rows_sweep.sh): 1: 864, 2: 600, 3: 524, 4: 504, 6: 578, 8: 566, 16: 761 us
+#undef ASM_GO
+    } else {
+        assemble_visual_kernel<<<(unsigned)scd_cdiv(rows, 4), 256, 0, st>>>(patch, patch_b, cls, pos, registers, nreg, rows, batch, T, width,
+                                                                             lg, lb, eps, x, stats);
+    }
+}
+
 extern "C" int scd_vit_encode_image(scd_handle h, const scd_encoder* e, const void* pixels, int dtype, int batch, void* out,
                                     int normalize, void* ws, size_t ws_bytes, void* stream_) {
     SCD_REQUIRE(h && e && pixels && out && ws && batch > 0, "scd_vit_encode_image: bad arguments");
@@ -1404,25 +1460,9 @@ extern "C" int scd_vit_encode_image(scd_handle h, const scd_encoder* e, const vo
         rc = scd_gemm_launch(cols, (const half_t*)e->w[W_PATCH], nullptr, nullptr, w.y, pad.prows, d.width, kk, SCD_ACT_NONE, st);
     }
     if (rc) return rc;
-    const long long rows = pad.rows;
-    static const int asm_rb = getenv("SCD_ASSEMBLE_ROWS") ? atoi(getenv("SCD_ASSEMBLE_ROWS")) : 4;     // 1: one row per wave (round 1-5 kernel; A/B, same bits); 8: eight
-    if (asm_rb > 1 && d.width <= 1024) {
-#define ASM_GO(RB)                                                                                                                        \
-    do {                                                                                                                                  \
-        const long long items = (long long)d.tokens * ((batch + RB - 1) / RB) + (rows - (long long)batch * d.tokens);                     \
-        assemble_visual_rows_kernel<RB><<<(unsigned)scd_cdiv(items, 4), 256, 0, st>>>(w.y, (const float*)e->w[W_PATCH_B], (const float*)e->w[W_CLS], \
-                                                                                      (const float*)e->w[W_POS], rows, batch, d.tokens, d.width,      \
-                                                                                      (const float*)e->w[W_LNPRE_W], (const float*)e->w[W_LNPRE_B],   \
-                                                                                      d.ln_eps, w.x, ln_fused(e, pad) ? w.stats_a : nullptr);          \
-    } while (0)
-        if (asm_rb == 8) ASM_GO(8); else ASM_GO(4);       // measured (tools/asm_rows_sweep.sh): 1: 864, 2: 600, 3: 524, 4: 504, 6: 578, 8: 566, 16: 761 us
-#undef ASM_GO
-    } else {
-        assemble_visual_kernel<<<(unsigned)scd_cdiv(rows, 4), 256, 0, st>>>(w.y, (const float*)e->w[W_PATCH_B], (const float*)e->w[W_CLS],
-                                                                             (const float*)e->w[W_POS], rows, batch, d.tokens, d.width,
-                                                                             (const float*)e->w[W_LNPRE_W], (const float*)e->w[W_LNPRE_B],
-                                                                             d.ln_eps, w.x, ln_fused(e, pad) ? w.stats_a : nullptr);
-    }
+    launch_assemble(w.y, (const float*)e->w[W_PATCH_B], (const float*)e->w[W_CLS], (const float*)e->w[W_POS],
+                    d.registers > 0 ? (const float*)e->w[w_registers(d)] : nullptr, d.registers, pad.rows, batch, d.tokens, d.width,
+                    (const float*)e->w[W_LNPRE_W], (const float*)e->w[W_LNPRE_B], d.ln_eps, w.x, ln_fused(e, pad) ? w.stats_a : nullptr, st);
     cls_rows_kernel<<<(pad.bh + 255) / 256, 256, 0, st>>>(w.rows, pad.bh, d.tokens, batch, 0);
     bool selected = false;
     rc = run_blocks(e, w, pad, st, &selected);
@@ -1483,6 +1523,24 @@ extern "C" int scd_attention_single_query_f16(scd_handle h, const void* kv, cons
     const int items = batch * heads;
     attention_single_query_kernel<<<(unsigned)scd_cdiv(items, 4), 256, 0, (hipStream_t)stream>>>((const half_t*)kv, (const half_t*)q, qrow,
                                                                                                  (half_t*)out, T, width, heads, items, causal != 0);
+    SCD_LAUNCH_CHECK();
+    return SCD_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ token assembly entry point (tests)
+// launch_assemble on caller buffers, without ln_pre (the kind-2 towers have none).  out has batch*T rows rounded up to 256, as the
+// towers' residual stream has; the rows behind batch*T are written as zeros.
+extern "C" int scd_vit_assemble_f16(scd_handle h, const void* patch, const float* patch_bias, const float* cls, const float* pos,
+                                    const float* registers, int nreg, int batch, int T, int width, void* out, int64_t* stats, void* stream) {
+    SCD_DEVICE_ENTRY(h, "scd_vit_assemble_f16");
+    SCD_REQUIRE(patch && cls && pos && out, "scd_vit_assemble_f16: null argument");
+    SCD_REQUIRE(batch > 0 && width > 0 && width % 256 == 0 && width <= 1024, "scd_vit_assemble_f16: batch %d, width %d (a multiple of 256, at most 1024)",
+                batch, width);
+    SCD_REQUIRE(nreg >= 0 && T >= 2 + nreg && (nreg == 0 || registers), "scd_vit_assemble_f16: T = %d needs 1 + nreg = %d + at least one patch row%s",
+                T, nreg, nreg > 0 && !registers ? " (registers is null)" : "");
+    const long long rows = ((long long)batch * T + 255) / 256 * 256;
+    launch_assemble((const half_t*)patch, patch_bias, cls, pos, registers, nreg, rows, batch, T, width, nullptr, nullptr, 0.f, (half_t*)out,
+                    (long long*)stats, (hipStream_t)stream);
     SCD_LAUNCH_CHECK();
     return SCD_OK;
 }

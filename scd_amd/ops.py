@@ -1174,6 +1174,28 @@ def attention_f16(qkv, batch, T, heads, causal=False):
     return out
 
 
+def vit_assemble_f16(patch, patch_bias, cls, pos, registers, batch, T, stats=False):
+    """The visual towers' token assembly (scd_vit_assemble_f16): patch fp16 [batch*np, width] (np = T - 1 - nreg), patch_bias float32
+    [width] or None, cls float32 [width], pos float32 [1 + np, width], registers float32 [nreg, width] or None -> out fp16 [rows_pad,
+    width] with rows_pad = batch*T rounded up to 256 (the rows behind batch*T are zeros); stats=True also returns the rows' int64
+    [rows_pad, 2] LayerNorm statistics."""
+    _need_cuda(patch)
+    _f16c(patch)
+    width = patch.shape[1]
+    nreg = 0 if registers is None else registers.shape[0]
+    np_ = T - 1 - nreg
+    _f32c(cls, pos, *[t for t in (patch_bias, registers) if t is not None])
+    assert patch.shape == (batch * np_, width) and cls.shape == (width,) and pos.shape == (1 + np_, width)
+    assert patch_bias is None or patch_bias.shape == (width,)
+    assert registers is None or (nreg > 0 and registers.shape == (nreg, width))
+    rows = (batch * T + 255) // 256 * 256
+    out = torch.empty((rows, width), dtype=torch.float16, device=patch.device)
+    st = torch.empty((rows, 2), dtype=torch.int64, device=patch.device) if stats else None
+    check(_L().scd_vit_assemble_f16(handle(), ptr(patch), ptr(patch_bias), ptr(cls), ptr(pos), ptr(registers), nreg, int(batch), int(T),
+                                    width, ptr(out), ptr(st), stream_ptr()))
+    return (out, st) if stats else out
+
+
 def attention_single_query_f16(kv, q, qrow, T, heads, causal=False):
     """The last block's one-query attention (scd_attention_single_query_f16): kv fp16 [batch*T, 2*width], q fp16 [batch, width],
     qrow int32 [batch] = b*T + query position (the causal key limit) -> out fp16 [batch, width]."""
