@@ -429,6 +429,33 @@ int scd_link_components(scd_handle h, int64_t n, const int32_t* ea, const int32_
 int scd_segment_mean_unit(scd_handle h, const float* X, int64_t n, const int32_t* order, const int64_t* offsets, int k, int d,
                           float* mean_out, float* unit_out, void* stream);
 
+/* ---- exact k nearest neighbours under the inner product, and the k-NN vote (no counterpart in the reference; the weighted k-NN protocol
+ * of DINO, Caron et al., ICCV 2021, section 4.1, and scikit-learn's NearestNeighbors(metric='cosine', algorithm='brute') /
+ * KNeighborsClassifier on unit rows; docs/design/knn.md) ---- */
+/* Queries Q [m, d] and base rows X [n, d], float32.  For query i: the k admissible columns j with the largest dot(Q_i, X_j), the dot taken
+ * in float64 on the fp32 rows (scd_first_neighbor's and scd_pair_dist_f64's dot: a pair has one value everywhere), ordered by (value
+ * descending, column ascending); a tie at the k-th place goes to the lower column.  self_base: -1, or the row of X that query 0 is
+ * (0 <= self_base, self_base + m <= n); query i then never returns column self_base + i.  Q = X with self_base = 0 is the k-NN graph,
+ * Q = X + a * d with self_base = a a row shard of it.  idx_out int32 [m, k], dot_out double [m, k], info_out int32 [4] = {rows that took
+ * the exact full-row pass, 1 if a value did not fit fp16 (then every row takes it), rows whose candidate slots overflowed, the largest
+ * candidate count of a row}.  Two fp16 MFMA passes with an error bound computed from the rows propose candidates, float64 decides; the
+ * result never depends on them; two calls return the same bits.  Inputs must be finite.  Cosine k-NN is this call on unit rows.
+ * Limits: 1 <= m < 2^31, 2 <= n < 2^31, d rounded up to 32 <= 1024, 1 <= k <= 64 and k <= the admissible columns (n, or n - 1 with
+ * self_base >= 0); scd_knn_ws_bytes returns 0 outside them.  The workspace holds the fp16 copies of X and Q and scd_knn_slots() int32
+ * candidate slots per query: 0.69 GB at m = n = 126,976, d = 768, k = 20. */
+size_t scd_knn_ws_bytes(int64_t m, int64_t n, int d, int k);
+int scd_knn_slots(void);
+int scd_knn(scd_handle h, const float* Q, int64_t m, const float* X, int64_t n, int d, int k, int64_t self_base, int32_t* idx_out,
+            double* dot_out, int32_t* info_out, void* ws, size_t ws_bytes, void* stream);
+/* The vote of the first k_use neighbours of each query (idx int32 [m, k_stride] and dot double [m, k_stride] as scd_knn returns them)
+ * with the labels base_labels int32 [n] of the base rows.  mode 0, uniform: the class with the most neighbours, ties to the lowest class
+ * (KNeighborsClassifier(weights='uniform')); score_out = the count.  mode 1, softmax: class score = the sum over its neighbours, in
+ * neighbour order, of exp((dot_j - dot_0) / temperature) in float64, the largest wins, ties to the lowest class.  A neighbour with a
+ * negative label or an index outside [0, n) does not vote; a query without a voting neighbour gets pred_out = -1 and score_out = 0.
+ * Any label range: no per-class table, O(k_use^2) work per query. */
+int scd_knn_vote(scd_handle h, const int32_t* idx, const double* dot, int64_t m, int k_stride, int k_use, const int32_t* base_labels,
+                 int64_t n, int mode, double temperature, int32_t* pred_out, double* score_out, void* stream);
+
 /* ---- host solvers (CPU, synchronous) ---- */
 /* linear_assignment (gcd/project_utils/cluster_utils.py:234-493), same tie-breaking; pairs_out [min(n,m),2] sorted */
 int scd_munkres(const int64_t* cost, int n, int m, int64_t* pairs_out, int* n_pairs_out);

@@ -140,6 +140,12 @@ SIGNATURES = {
     "scd_link_components": (_i, [_vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _sz, _vp]),
     # h, X, n, order, offsets, k, d, mean_out, unit_out, stream
     "scd_segment_mean_unit": (_i, [_vp, _vp, _i64, _vp, _vp, _i, _i, _vp, _vp, _vp]),
+    "scd_knn_ws_bytes": (_sz, [_i64, _i64, _i, _i]),
+    "scd_knn_slots": (_i, []),
+    # h, Q, m, X, n, d, k, self_base, idx_out, dot_out, info_out, ws, ws_bytes, stream
+    "scd_knn": (_i, [_vp, _vp, _i64, _vp, _i64, _i, _i, _i64, _vp, _vp, _vp, _vp, _sz, _vp]),
+    # h, idx, dot, m, k_stride, k_use, base_labels, n, mode, temperature, pred_out, score_out, stream
+    "scd_knn_vote": (_i, [_vp, _vp, _vp, _i64, _i, _i, _vp, _i64, _i, C.c_double, _vp, _vp, _vp]),
     "scd_munkres": (_i, [_vp, _i, _i, _vp, C.POINTER(_i)]),
     "scd_munkres_sparse": (_i, [_i, _i64, _vp, _vp, _vp, _vp, C.POINTER(_i)]),
     "scd_transport_solve": (_i, [_vp, _i64, _i, _i, _i, _vp, C.POINTER(_i64)]),

@@ -957,6 +957,46 @@ def segment_mean_unit(x, order, offsets):
     return mean, unit
 
 
+# ----------------------------------------------------------------------------- exact k nearest neighbours (docs/design/knn.md)
+def knn(q, x, k, self_base=-1):
+    """scd_knn: queries q float32 [m, d] and base rows x float32 [n, d] on the device -> (idx int32 [m, k], dot float64 [m, k], info
+    int32 [4] = rows through the exact full-row pass, fp16-overflow flag, rows whose candidate slots overflowed, largest candidate
+    count), all on the device.  Row i: the k columns j != self_base + i with the largest float64 dot, ordered by (dot descending,
+    column ascending).  self_base = -1 excludes nothing; q a view of rows a .. a + m of x with self_base = a is a shard of the graph."""
+    _need_cuda(q, x)
+    if q.dim() != 2 or x.dim() != 2 or q.dtype != torch.float32 or x.dtype != torch.float32 or q.shape[1] != x.shape[1]:
+        raise _lib.ScdError(_lib.SCD_EINVAL, "knn: q and x must be float32 [m, d] and [n, d]")
+    q, x = q.contiguous(), x.contiguous()
+    (m, d), n, k = q.shape, x.shape[0], int(k)
+    idx = torch.empty((m, max(k, 0)), dtype=torch.int32, device=x.device)
+    dot = torch.empty((m, max(k, 0)), dtype=torch.float64, device=x.device)
+    info = torch.empty(4, dtype=torch.int32, device=x.device)
+    nb = _L().scd_knn_ws_bytes(m, n, d, k)
+    ws = _ws(max(nb, 16), x.device)
+    check(_L().scd_knn(handle(), ptr(q), m, ptr(x), n, d, k, int(self_base), ptr(idx), ptr(dot), ptr(info), ptr(ws), nb, stream_ptr()))
+    return idx, dot, info
+
+
+KNN_UNIFORM, KNN_SOFTMAX = 0, 1
+
+
+def knn_vote(idx, dot, base_labels, k_use=None, mode=KNN_SOFTMAX, temperature=0.07):
+    """scd_knn_vote: idx int32 [m, k] and dot float64 [m, k] as `knn` returns them, base_labels int32 [n] -> (pred int32 [m], score
+    float64 [m]).  The first k_use neighbours vote: KNN_UNIFORM counts, KNN_SOFTMAX weights exp((dot_j - dot_0) / temperature); the
+    largest class score wins, ties to the lowest class; negative labels do not vote and a query without a vote gets -1."""
+    _need_cuda(idx, dot, base_labels)
+    if idx.dim() != 2 or idx.shape != dot.shape or idx.dtype != torch.int32 or dot.dtype != torch.float64 or base_labels.dtype != torch.int32:
+        raise _lib.ScdError(_lib.SCD_EINVAL, "knn_vote: idx int32 [m, k], dot float64 [m, k], base_labels int32 [n]")
+    idx, dot, base_labels = idx.contiguous(), dot.contiguous(), base_labels.contiguous()
+    m, k = idx.shape
+    k_use = k if k_use is None else int(k_use)
+    pred = torch.empty(m, dtype=torch.int32, device=idx.device)
+    score = torch.empty(m, dtype=torch.float64, device=idx.device)
+    check(_L().scd_knn_vote(handle(), ptr(idx), ptr(dot), m, k, k_use, ptr(base_labels), base_labels.numel(), int(mode), float(temperature),
+                            ptr(pred), ptr(score), stream_ptr()))
+    return pred, score
+
+
 # ----------------------------------------------------------------------------- host solvers
 def munkres(cost):
     """linear_assignment (cluster_utils.py:234): int array [n,m] -> sorted pairs [min(n,m),2]."""
