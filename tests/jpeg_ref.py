@@ -7,26 +7,44 @@ import numpy as np
 ZIGZAG = [0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14, 21, 28, 35, 42, 49, 56,
           57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63]
 
-PLANTS = ("replicate", "swap_rounding", "unclamped_row", "padded_last_col", "clamp_range", "restart_keeps_pred")
+PLANTS = ("replicate", "swap_rounding", "unclamped_row", "padded_last_col", "clamp_range", "restart_keeps_pred", "adobe_ignored",
+          "gray_sampling_used", "first_table_wins", "first_dri_wins", "zrl_15", "pad_ones_required", "table_id_masked")
+# Plants that change how the stream is read.  A reader that loses the stream under one of them (an undefined code, an index past 63, a
+# missing marker) stops there and leaves the remaining blocks zero, as a decoder that conceals errors would: the mistake then shows
+# as pixels, which is what the sensitivity test looks at.
+_STREAM_PLANTS = ("gray_sampling_used", "first_table_wins", "first_dri_wins", "zrl_15", "pad_ones_required", "table_id_masked")
 
 
 class Rejected(Exception):
     """The range guard tripped (the only rejection this restatement models)."""
 
 
-def _header(d):
-    q, huff, ri, sof, p = {}, {}, 0, None, 2
+def _header(d, plant=None):
+    """Tables, restart interval, frame, the scan's table selectors, the scan's first byte, and what the APPn segments say about colour
+    (jfif, adobe transform or None).  A later DQT, DHT or DRI replaces an earlier one; 0xFF fill bytes may precede any marker."""
+    q, huff, ri, sof, p = {}, {}, None, None, 2
+    jfif, adobe = False, None
+    tid = (lambda t: t & 1) if plant == "table_id_masked" else (lambda t: t)
+    keep_first = plant == "first_table_wins"
     while True:
         assert d[p] == 0xFF
+        while d[p + 1] == 0xFF:
+            p += 1
         m, ln = d[p + 1], (d[p + 2] << 8) | d[p + 3]
         s = d[p + 4:p + 2 + ln]
-        if m == 0xDB:
+        if m == 0xE0:
+            jfif = jfif or (len(s) >= 14 and s[:5] == b"JFIF\0")
+        elif m == 0xEE:
+            if len(s) >= 12 and s[:5] == b"Adobe":
+                adobe = s[11]
+        elif m == 0xDB:
             o = 0
             while o < len(s):
                 pq, tq = s[o] >> 4, s[o] & 15
                 n = 128 if pq else 64
                 t = s[o + 1:o + 1 + n]
-                q[tq] = [(t[2 * k] << 8) | t[2 * k + 1] for k in range(64)] if pq else list(t)
+                if not (keep_first and tid(tq) in q):
+                    q[tid(tq)] = [(t[2 * k] << 8) | t[2 * k + 1] for k in range(64)] if pq else list(t)
                 o += 1 + n
         elif m == 0xC4:
             o = 0
@@ -41,16 +59,18 @@ def _header(d):
                         code += 1
                         k += 1
                     code <<= 1
-                huff[(s[o] >> 4, s[o] & 15)] = table
+                if not (keep_first and (s[o] >> 4, tid(s[o] & 15)) in huff):
+                    huff[(s[o] >> 4, tid(s[o] & 15))] = table
                 o += 17 + total
         elif m == 0xDD:
-            ri = (s[0] << 8) | s[1]
+            if not (plant == "first_dri_wins" and ri is not None):
+                ri = (s[0] << 8) | s[1]
         elif m in (0xC0, 0xC1):
-            sof = dict(h=(s[1] << 8) | s[2], w=(s[3] << 8) | s[4], comps=[(s[6 + 3 * c], s[7 + 3 * c] >> 4, s[7 + 3 * c] & 15, s[8 + 3 * c])
+            sof = dict(h=(s[1] << 8) | s[2], w=(s[3] << 8) | s[4], comps=[(s[6 + 3 * c], s[7 + 3 * c] >> 4, s[7 + 3 * c] & 15, tid(s[8 + 3 * c]))
                                                                           for c in range(s[5])])
         elif m == 0xDA:
-            sel = [(s[2 + 2 * c] >> 4, s[2 + 2 * c] & 15) for c in range(s[0])]
-            return q, huff, ri, sof, sel, p + 2 + ln
+            sel = [(tid(s[2 + 2 * c] >> 4), tid(s[2 + 2 * c] & 15)) for c in range(s[0])]
+            return q, huff, ri or 0, sof, sel, p + 2 + ln, jfif, adobe
         p += 2 + ln
 
 
@@ -89,7 +109,8 @@ class _Bits:
         r = self.bits(s)
         return r if r >= (1 << (s - 1)) else r - (1 << s) + 1
 
-    def restart(self, n):
+    def restart(self, n, pad_ones_required=False):
+        assert not pad_ones_required or self.acc & ((1 << self.n) - 1) == (1 << self.n) - 1      # the unread bits: pad bits of either value
         self.n = 0
         assert self.d[self.pos] == 0xFF and self.d[self.pos + 1] == 0xD0 + (n & 7)
         self.pos += 2
@@ -114,11 +135,11 @@ def _pass(v, shift):
 
 
 def idct(coef, clamp_range=False, guard=True):
-    """coef int [8, 8] (dequantised, natural order) -> uint8 [8, 8]."""
+    """coef int [..., 8, 8] (dequantised, natural order) -> uint8 [..., 8, 8]."""
     c = np.asarray(coef, dtype=np.int64)
     if guard and np.abs(c).max() > 4096:
         raise Rejected("coefficient")
-    ws = _pass(c.T, 11).T                      # down the columns
+    ws = np.swapaxes(_pass(np.swapaxes(c, -1, -2), 11), -1, -2)                      # down the columns
     if guard and np.abs(ws).max() > 8192:
         raise Rejected("column pass")
     x = _pass(ws, 18)
@@ -158,21 +179,14 @@ def _upsample(p, hs, vs, w, h, plant):
     return out[:, :w]
 
 
-def decode(data, plant=None, guard=True):
-    """JPEG bytes -> uint8 [h, w, 3] by the rules; plant: one of PLANTS (or None); guard: apply the range guard (Rejected)."""
-    assert plant is None or plant in PLANTS
-    d = bytes(data)
-    q, huff, ri, sof, sel, pos = _header(d)
-    w, h, comps = sof["w"], sof["h"], sof["comps"]
+def _scan(d, pos, q, huff, ri, comps, sel, hs, vs, mx, n_mcu, plant, blocks):
+    """The entropy-coded segment: appends (component, block column, block row, 64 dequantised coefficients in natural order)."""
     nc = len(comps)
-    hs, vs = (comps[0][1], comps[0][2]) if nc == 3 else (1, 1)
-    mx, my = -(-w // (8 * hs)), -(-h // (8 * vs))
-    planes = [np.zeros((my * 8 * (vs if c == 0 else 1), mx * 8 * (hs if c == 0 else 1)), dtype=np.uint8) for c in range(nc)]
     layout = [(0, bx, by) for by in range(vs) for bx in range(hs)] + [(c, 0, 0) for c in range(1, nc)]
     bits, pred = _Bits(d, pos), [0] * nc
-    for m in range(mx * my):
+    for m in range(n_mcu):
         if ri and m and m % ri == 0:
-            bits.restart(m // ri - 1)
+            bits.restart(m // ri - 1, plant == "pad_ones_required")
             if plant != "restart_keeps_pred":
                 pred = [0] * nc
         for c, bx, by in layout:
@@ -190,16 +204,46 @@ def decode(data, plant=None, guard=True):
                     coef[ZIGZAG[k]] = bits.value(s) * qt[k]
                     k += 1
                 elif r == 15:
-                    k += 16
+                    k += 15 if plant == "zrl_15" else 16
                 else:
                     break
             fx, fy = (hs, vs) if c == 0 else (1, 1)
-            y0, x0 = ((m // mx) * fy + by) * 8, ((m % mx) * fx + bx) * 8
-            planes[c][y0:y0 + 8, x0:x0 + 8] = idct(np.array(coef).reshape(8, 8), plant == "clamp_range", guard)
+            blocks.append((c, (m % mx) * fx + bx, (m // mx) * fy + by, coef))
+
+
+def decode(data, plant=None, guard=True):
+    """JPEG bytes -> uint8 [h, w, 3] by the rules; plant: one of PLANTS (or None); guard: apply the range guard (Rejected)."""
+    assert plant is None or plant in PLANTS
+    d = bytes(data)
+    q, huff, ri, sof, sel, pos, jfif, adobe = _header(d, plant)
+    w, h, comps = sof["w"], sof["h"], sof["comps"]
+    nc = len(comps)
+    # a one-component scan is one block per MCU whatever the frame's sampling factors say
+    hs, vs = (comps[0][1], comps[0][2]) if nc == 3 or plant == "gray_sampling_used" else (1, 1)
+    mx, my = -(-w // (8 * hs)), -(-h // (8 * vs))
+    planes = [np.zeros((my * 8 * (vs if c == 0 else 1), mx * 8 * (hs if c == 0 else 1)), dtype=np.uint8) for c in range(nc)]
+    blocks = []
+    try:
+        _scan(d, pos, q, huff, ri, comps, sel, hs, vs, mx, mx * my, plant, blocks)
+    except (AssertionError, IndexError, KeyError):
+        if plant not in _STREAM_PLANTS:
+            raise
+    if blocks:
+        px = idct(np.array([b[3] for b in blocks]).reshape(-1, 8, 8), plant == "clamp_range", guard)
+        for (c, bx, by, _), p8 in zip(blocks, px):
+            planes[c][8 * by:8 * by + 8, 8 * bx:8 * bx + 8] = p8
+    if nc == 3:
+        # libjpeg's default_decompress_parms: JFIF means YCbCr whatever Adobe says; else Adobe's transform; else the component ids
+        ycc = jfif or adobe == 1 or (adobe is None and [c[0] for c in comps] == [1, 2, 3])
+        if plant == "adobe_ignored":
+            ycc = adobe != 0                  # the plant: an Adobe transform 0 means RGB although a JFIF segment stands beside it
+        assert ycc or plant == "adobe_ignored", "outside the decoder's scope: not YCbCr with certainty"
     yy = planes[0][:h, :w].astype(np.int64)
     if nc == 1:
         return np.repeat(yy[:, :, None], 3, 2).astype(np.uint8)
     cb = _upsample(planes[1], hs, vs, w, h, plant) - 128
     cr = _upsample(planes[2], hs, vs, w, h, plant) - 128
+    if not ycc:
+        return np.stack([yy, cb + 128, cr + 128], -1).astype(np.uint8)
     rgb = np.stack([yy + ((91881 * cr + 32768) >> 16), yy + ((-22554 * cb - 46802 * cr + 32768) >> 16), yy + ((116130 * cb + 32768) >> 16)], -1)
     return np.clip(rgb, 0, 255).astype(np.uint8)

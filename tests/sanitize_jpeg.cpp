@@ -1,12 +1,12 @@
 // Host-side driver for the JPEG parser, table builder and CPU decoder (scd_amd/csrc/jpeg.hip, jpeg.h) under AddressSanitizer +
-// UndefinedBehaviorSanitizer: every fixture of tests/golden/jpeg_decode.npz, the corrupt ones included, must get the reason / status the
-// fixture records, and 1,000 seeded single-byte corruptions (one in eight of them in a Huffman table's counts) and truncations of them
+// UndefinedBehaviorSanitizer: every fixture of tests/golden/jpeg_decode.npz and of tests/golden/jpeg_decode_foreign.npz, the corrupt ones
+// included, must get the reason / status the fixture records, and 1,000 seeded single-byte corruptions (one in eight of them in a Huffman table's counts) and truncations of them
 // must all return without a sanitizer report.  The functions it drives are the ones the kernels run, so the device sees these bytes
 // only after this program has.
 //
 //   clang++ -x c++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -D__HIP_PLATFORM_AMD__
 //       -I/opt/rocm/include -Iinclude -Iscd_amd/csrc scd_amd/csrc/jpeg.hip tests/sanitize_jpeg.cpp -o sanitize_jpeg
-//   ./sanitize_jpeg tests/golden/jpeg_decode.npz
+//   ./sanitize_jpeg tests/golden/jpeg_decode.npz tests/golden/jpeg_decode_foreign.npz
 #include <stdarg.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -110,14 +110,21 @@ static int run_one(const uint8_t* bytes, size_t len, int* status) {
     return info.reason;
 }
 
-int main(int argc, char** argv) {
-    const char* path = argc > 1 ? argv[1] : "tests/golden/jpeg_decode.npz";
+// The cases of one fixture file: every one must get the reason / status the file records.  Returns the failures, or -1 when the file
+// cannot be read.  `fx` receives the file's bytes and case offsets, for the corruption rounds.
+struct Fixtures {
+    std::vector<uint8_t> z;
+    const uint8_t* data = nullptr;
+    std::vector<size_t> off;
+};
+
+static int run_file(const char* path, Fixtures* fx) {
     FILE* f = fopen(path, "rb");
     if (!f) {
         printf("cannot open %s\n", path);
-        return 2;
+        return -1;
     }
-    std::vector<uint8_t> z;
+    std::vector<uint8_t>& z = fx->z;
     uint8_t buf[65536];
     for (size_t n; (n = fread(buf, 1, sizeof(buf), f)) > 0;) z.insert(z.end(), buf, buf + n);
     fclose(f);
@@ -125,29 +132,52 @@ int main(int argc, char** argv) {
     size_t nb, nl, nm;
     if (!npz_member(z, "data", &data, &nb) || !npz_member(z, "data_len", &lens, &nl) || !npz_member(z, "meta", &meta, &nm)) {
         printf("%s: not the uncompressed fixture file expected\n", path);
-        return 2;
+        return -1;
     }
     const size_t n = nl / 8;
     if (nm != n * 32) {
-        printf("meta has %zu bytes for %zu cases\n", nm, n);
-        return 2;
+        printf("%s: meta has %zu bytes for %zu cases\n", path, nm, n);
+        return -1;
     }
-    std::vector<size_t> off(n + 1, 0);
-    for (size_t i = 0; i < n; ++i) off[i + 1] = off[i] + (size_t)le(lens + 8 * i, 8);
-    if (off[n] != nb) {
-        printf("data has %zu bytes, lengths sum to %zu\n", nb, off[n]);
-        return 2;
+    fx->data = data;
+    fx->off.assign(n + 1, 0);
+    for (size_t i = 0; i < n; ++i) fx->off[i + 1] = fx->off[i] + (size_t)le(lens + 8 * i, 8);
+    if (fx->off[n] != nb) {
+        printf("%s: data has %zu bytes, lengths sum to %zu\n", path, nb, fx->off[n]);
+        return -1;
     }
     int failures = 0;
     for (size_t i = 0; i < n; ++i) {
         int st;
-        const int reason = run_one(data + off[i], off[i + 1] - off[i], &st);
+        const int reason = run_one(data + fx->off[i], fx->off[i + 1] - fx->off[i], &st);
         const int want_reason = (int)(int32_t)le(meta + 32 * i, 4), want_status = (int)(int32_t)le(meta + 32 * i + 4, 4);
         if (reason != want_reason || (reason == 0 && st != want_status)) {
-            printf("case %zu: reason %d status %d, expected %d / %d\n", i, reason, st, want_reason, want_status);
+            printf("%s case %zu: reason %d status %d, expected %d / %d\n", path, i, reason, st, want_reason, want_status);
             ++failures;
         }
     }
+    return failures;
+}
+
+// Usage: sanitize_jpeg [fixture file ...].  Every case of every file is run; the corruptions are drawn from the first file's cases.
+int main(int argc, char** argv) {
+    const char* fallback[] = {argv[0], "tests/golden/jpeg_decode.npz"};
+    if (argc < 2) {
+        argv = (char**)fallback;
+        argc = 2;
+    }
+    std::vector<Fixtures> files((size_t)argc - 1);
+    int failures = 0;
+    size_t fixtures = 0;
+    for (int a = 1; a < argc; ++a) {
+        const int r = run_file(argv[a], &files[(size_t)a - 1]);
+        if (r < 0) return 2;
+        failures += r;
+        fixtures += files[(size_t)a - 1].off.size() - 1;
+    }
+    const uint8_t* data = files[0].data;
+    const std::vector<size_t>& off = files[0].off;
+    const size_t n = off.size() - 1;
     int accepted = 0, rejected = 0, status_nz = 0;
     for (int t = 0; t < 1000; ++t) {
         const size_t i = rnd((uint32_t)n);
@@ -174,7 +204,7 @@ int main(int argc, char** argv) {
         else
             ++accepted;
     }
-    printf("%zu fixtures, 1000 corruptions (%d decoded, %d parser rejects, %d decoder rejects), %ld calls returned, %d failures\n", n, accepted,
+    printf("%zu fixtures, 1000 corruptions (%d decoded, %d parser rejects, %d decoder rejects), %ld calls returned, %d failures\n", fixtures, accepted,
            rejected, status_nz, g_calls, failures);
     return failures ? 1 : 0;
 }

@@ -1,5 +1,7 @@
-"""The device JPEG decoder (scd_amd/jpeg.py, scd_amd/csrc/jpeg.hip) against Pillow's pixels in tests/golden/jpeg_decode.npz, its
-status path on the reject fixtures, and decode='device' of the ingest path against decode='pil' (docs/design/ingest.md)."""
+"""The device JPEG decoder (scd_amd/jpeg.py, scd_amd/csrc/jpeg.hip) against Pillow's pixels in tests/golden/jpeg_decode.npz (files
+Pillow's encoder wrote, up to 250 x 187) and tests/golden/jpeg_decode_foreign.npz (photograph sizes, scans laid against the entropy
+kernel's byte window, other encoders' headers and streams), its status path on the reject fixtures, and decode='device' of the ingest
+path against decode='pil' (docs/design/ingest.md)."""
 import hashlib
 import os
 import sys
@@ -9,7 +11,7 @@ import pytest
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from jpeg_cases import ACCEPTED, CASES  # noqa: E402
+from jpeg_cases import ACCEPTED, CASES, FOREIGN, FOREIGN_ACCEPTED, first_bad_band  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 pytestmark = pytest.mark.gpu
@@ -26,7 +28,8 @@ def _check(case, got):
     assert got.dtype == np.uint8 and got.shape == (case.h, case.w, 3), case.name
     if case.pixels is not None:
         assert np.array_equal(got, case.pixels), case.name
-    assert hashlib.sha256(np.ascontiguousarray(got).tobytes()).hexdigest() == case.sha, case.name
+    assert hashlib.sha256(np.ascontiguousarray(got).tobytes()).hexdigest() == case.sha, (case.name, "first band that differs",
+                                                                                            first_bad_band(case, got))
 
 
 @pytest.fixture(scope="module")
@@ -85,6 +88,88 @@ def test_unsupported_file_is_the_callers_to_sort_out():
     prog = next(c for c in CASES if c.name == "rej_progressive")
     with pytest.raises(jpeg.JpegUnsupported):
         jpeg.JpegDecoder().decode([ACCEPTED[0].data, prog.data])
+
+
+# ------------------------------------------------------------------------------------------------ the second fixture file
+def _interleaved():
+    """Every accepted case of the second file with the accepted cases of the first between them."""
+    out = []
+    for k, c in enumerate(FOREIGN_ACCEPTED):
+        out.append(c)
+        out += ACCEPTED[k:k + 1]
+    return out + ACCEPTED[len(FOREIGN_ACCEPTED):]
+
+
+@pytest.fixture(scope="module")
+def foreign_batch():
+    """The mixed batch, decoded once and shared: (cases, images, status)."""
+    assert torch.cuda.is_available(), "GPU tests need a HIP device"
+    order = _interleaved()
+    images, status = _decode([c.data for c in order])
+    return order, images, status
+
+
+def test_foreign_fixtures_mixed_with_the_old_in_one_batch(foreign_batch):
+    """Photograph sizes and strips (the second to fifth trip of the colour kernel's x loop, 18 trips of its y loop), groups of blocks
+    that read past the LDS window into global memory, stuffed pairs and RSTn markers across the window's end and across a 16-byte
+    line, and the header and stream variants of other encoders: all equal to Pillow, status 0.  A large image that differs is reported
+    with its first band of 16 rows that does."""
+    order, images, status = foreign_batch
+    assert len(order) == len(FOREIGN_ACCEPTED) + len(ACCEPTED) and len(FOREIGN_ACCEPTED) >= 80
+    assert status.dtype == np.int32 and not status.any(), [(c.name, int(s)) for c, s in zip(order, status) if s]
+    for c, got in zip(order, images):
+        _check(c, got)
+
+
+def test_foreign_batch_reversed_gives_the_same_bytes(foreign_batch):
+    order, images, _ = foreign_batch
+    again, status = _decode([c.data for c in order[::-1]])
+    assert not status.any()
+    for c, a, b in zip(order, images, again[::-1]):
+        assert np.array_equal(a, b), c.name
+
+
+def test_window_and_size_cases_alone_and_last_in_a_batch(foreign_batch):
+    """Each window case and each size case as a batch of one, and each window case as the last file of a batch behind a file whose
+    length is no multiple of 16 (its window then ends in the data section's last bytes, which are loaded byte by byte): the same bytes
+    as in the mixed batch."""
+    order, images, _ = foreign_batch
+    mixed = {c.name: im for c, im in zip(order, images)}
+    before = next(c for c in ACCEPTED if len(c.data) % 16 != 0 and c.w <= 64)
+    solo = [c for c in FOREIGN_ACCEPTED if c.name.startswith(("win_", "size_"))]
+    assert len(solo) == 55
+    for c in solo:
+        got, status = _decode([c.data])
+        assert status.tolist() == [0], c.name
+        _check(c, got[0])
+        assert np.array_equal(got[0], mixed[c.name]), c.name
+        if c.name.startswith("win_"):
+            got, status = _decode([before.data, c.data])
+            assert status.tolist() == [0, 0], c.name
+            assert np.array_equal(got[0], mixed[before.name]) and np.array_equal(got[1], mixed[c.name]), c.name
+
+
+def test_foreign_status_cases_get_the_hosts_status_and_leave_the_rest_exact():
+    """A fill byte before an RSTn inside the scan, and an RSTn with the wrong number: Pillow decodes both, the entropy decoder follows
+    neither (marker_in_scan).  Between good files each gets the status the CPU decoder gives it, its pixels are not written, and its
+    neighbours are exact."""
+    assert torch.cuda.is_available(), "GPU tests need a HIP device"
+    from scd_amd import jpeg
+    bad = [c for c in FOREIGN if c.reason == 0 and c.status != 0]
+    assert [c.name for c in bad] == ["s_rst_fill", "s_rst_wrong_number"] and [c.status for c in bad] == [4, 4]
+    for c in bad:                                                   # the host first: the device sees only what the CPU run has ended on
+        with pytest.raises(jpeg.JpegDecodeError) as e:
+            jpeg.decode_jpeg_host(c.data)
+        assert e.value.status == c.status
+    good = [c for c in FOREIGN_ACCEPTED if c.name.startswith("s_")][:4]
+    order = [good[0], bad[0], good[1], good[2], bad[1], good[3]]
+    images, status = _decode([c.data for c in order])
+    assert status.tolist() == [c.status for c in order]
+    for c, got in zip(order, images):
+        if c.status:
+            assert not got.any(), c.name                            # untouched: the decoder's buffer starts as zeros
+        else:
+            _check(c, got)
 
 
 # ------------------------------------------------------------------------------------------------ ingest: decode='device' against 'pil'
@@ -150,6 +235,34 @@ def test_files_to_features_device_decode_equals_pil(tmp_path):
     assert errors["pil"] == errors["device"]
     with pytest.raises(ValueError, match="decode"):
         images.extract_features_from_files(paths, targets, mask_lab, models, decode="hardware")
+
+
+def test_files_to_features_device_decode_equals_pil_at_photograph_sizes(tmp_path):
+    """Six Pillow-written files at 500 x 375, 375 x 500 and 640 x 427, each size in two of the three samplings: every one is decoded
+    on the device and the features are those of decode='pil', bit for bit."""
+    assert torch.cuda.is_available(), "GPU tests need a HIP device"
+    Image = pytest.importorskip("PIL.Image")
+    from scd_amd import images
+    from scd_amd.clip import weights as W
+    from scd_amd.clip.model import CLIP
+    paths = []
+    for k, ((w, h), sub) in enumerate(zip([(500, 375), (375, 500), (640, 427)] * 2, (0, 1, 2, 2, 0, 1))):
+        rng = np.random.default_rng(300 + k)
+        yy, xx = np.mgrid[0:h, 0:w]
+        base = np.stack([(xx * (3 + c) + yy * (5 - c)) % 256 for c in range(3)], -1) + rng.integers(-40, 41, (h, w, 3))
+        paths.append(str(tmp_path / ("p%d.jpg" % k)))
+        Image.fromarray(np.clip(base, 0, 255).astype(np.uint8), "RGB").save(paths[-1], quality=(85, 60, 92)[k % 3], subsampling=sub,
+                                                                           **(dict(restart_marker_blocks=7) if k == 4 else {}))
+    n = len(paths)
+    targets, mask_lab = np.arange(n) % 3, np.arange(n) < 2
+    models = {"clip": CLIP(W.synthetic_clip_state_dict(seed=0, cfg=dict(v_layers=2, t_layers=2))).cuda()}
+    want = images.extract_features_from_files(paths, targets, mask_lab, models, batch_size=64, threads=3)["clip"]
+    for bs in (2, 64):
+        stats = {}
+        got = images.extract_features_from_files(paths, targets, mask_lab, models, batch_size=bs, threads=3, decode="device", stats=stats)["clip"]
+        assert stats == dict(files=6, device_decoded=6, fallback_parser=0, fallback_status=0), stats
+        for k in want:
+            assert got[k].dtype == want[k].dtype and np.array_equal(got[k], want[k]), (k, bs)
 
 
 def test_main_unsup_decode_device_writes_the_same_caches(tmp_path, monkeypatch):

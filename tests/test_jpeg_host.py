@@ -1,5 +1,7 @@
 """The JPEG parser and the CPU decoder (scd_amd/jpeg.py, scd_amd/csrc/jpeg.h / jpeg.hip; docs/design/ingest.md, "Device JPEG decode")
-against Pillow's pixels: tests/golden/jpeg_decode.npz (tools/gen_jpeg_golden.py) and, where Pillow is installed, freshly encoded files.
+against Pillow's pixels: tests/golden/jpeg_decode.npz (tools/gen_jpeg_golden.py), tests/golden/jpeg_decode_foreign.npz
+(tools/gen_jpeg_golden_foreign.py: photograph sizes, scans laid against the kernel's byte window, other encoders' headers and streams)
+and, where Pillow is installed, freshly encoded files.
 scd_jpeg_decode_host runs the functions the kernels run, so this is the device decoder's arithmetic on the CPU."""
 import hashlib
 import io
@@ -13,14 +15,16 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import jpeg_ref as R  # noqa: E402
-from jpeg_cases import ACCEPTED, CASES, GOLDEN, ROOT  # noqa: E402
+import jpeg_writer as W  # noqa: E402
+from jpeg_cases import (ACCEPTED, CASES, FOREIGN, FOREIGN_ACCEPTED, GOLDEN, GOLDEN_FOREIGN, HALF, LINE, ROOT, WIN, first_bad_band,  # noqa: E402
+                        window_starts)
 
 
 def check_pixels(case, got):
     assert got.dtype == np.uint8 and got.shape == (case.h, case.w, 3), case.name
     if case.pixels is not None:
         assert np.array_equal(got, case.pixels), case.name
-    assert hashlib.sha256(np.ascontiguousarray(got).tobytes()).hexdigest() == case.sha, case.name
+    assert hashlib.sha256(np.ascontiguousarray(got).tobytes()).hexdigest() == case.sha, (case.name, first_bad_band(case, got))
 
 
 def test_fixture_file_is_small_and_complete():
@@ -41,9 +45,124 @@ def test_fixture_file_is_small_and_complete():
         assert (c.pixels is not None) == (c.sha != "" and c.w <= 64 and c.h <= 64), c.name
 
 
+FOREIGN_NAMES = (
+    ["size_500x375_420", "size_375x500_422_rst", "size_1024x16_420", "size_1024x16_422", "size_1025x16_420", "size_1025x16_422", "size_257x9_444",
+     "size_640x8_gray", "size_16x1100_420", "size_8x1100_gray", "win_dense_8", "win_dense_24"] +
+    ["win_ff00_end_p%02d" % p for p in range(16)] + ["win_ff00_line_p%02d" % p for p in range(13)] +
+    ["win_rst_shift%02d" % c for c in (0, 5, 10, 15)] + ["win_ri%d_%s" % (r, s) for s in ("gray", "422") for r in (1, 2, 5, 8)] +
+    ["win_ri4_444", "win_ri4_420"] +
+    ["s_" + n for n in ("sof0_tables23", "sof1_tables23", "sof1_gray", "dqt16", "dqt16_gray", "gray_f22", "gray_f41", "gray_f14", "nojfif_ids123",
+                        "nojfif_ids012", "nojfif_idsRGB", "adobe0", "adobe1", "adobe1_ids012", "adobe2", "jfif_adobe0", "adobe0_jfif",
+                        "app0_not_jfif", "fill_header", "fill_gray", "trailing", "dri0", "dri_mcus", "dri_65535", "dri_twice", "dri_then_0",
+                        "redefined", "redefined_gray", "tables_after_sof", "unused_tables", "all_on_tables0", "luma1_chroma0", "dc1_ac0",
+                        "pad_zeros", "pad_zeros_gray", "zrl3_idx63", "zrl3_idx63_420", "idx63_no_eob", "dc_cat11", "huff16_unused", "rst_fill",
+                        "rst_wrong_number")])
+FOREIGN_REJECTED = {"s_nojfif_ids012": ("reason", 10), "s_nojfif_idsRGB": ("reason", 10), "s_adobe0": ("reason", 10), "s_adobe2": ("reason", 10),
+                    "s_rst_fill": ("status", 4), "s_rst_wrong_number": ("status", 4)}
+
+
+def test_foreign_fixture_file_is_small_and_complete():
+    """The second file: every case family of docs/design/ingest.md ("What the tests pin") by name, Pillow's pixels for every case
+    (the rejected ones too: Pillow decodes them all), band checksums for the large images, and the same size limit as the first."""
+    assert os.path.getsize(GOLDEN_FOREIGN) < 564 * 1024
+    assert [c.name for c in FOREIGN] == FOREIGN_NAMES
+    for c in FOREIGN:
+        assert c.sha != "" and (c.pixels is not None) == (c.w <= 64 and c.h <= 64), c.name
+        assert len(c.bands) == (0 if c.pixels is not None else -(-c.h // 16)), c.name
+        want = FOREIGN_REJECTED.get(c.name, ("reason", 0))
+        assert (c.reason, c.status) == ((want[1], 0) if want[0] == "reason" else (0, want[1])), c.name
+        assert c.name.startswith("size_") or len(c.data) < 12 * 1024, c.name
+    assert len(FOREIGN_ACCEPTED) == len(FOREIGN) - len(FOREIGN_REJECTED)
+
+
+def test_foreign_reject_cases_carry_exactly_the_recorded_code():
+    """Three components that are not YCbCr with certainty by libjpeg's default_decompress_parms rule are the parser's to refuse
+    (colourspace), although libjpeg guesses YCbCr for two of the four; a fill byte before an RSTn inside the scan and an RSTn with the
+    wrong number are the entropy decoder's (marker_in_scan).  Pillow decodes all six, and gets them."""
+    from scd_amd import jpeg
+    seen = {}
+    for c in FOREIGN:
+        try:
+            jpeg.decode_jpeg_host(c.data)
+        except jpeg.JpegUnsupported as e:
+            seen[c.name] = ("reason", e.reason)
+        except jpeg.JpegDecodeError as e:
+            seen[c.name] = ("status", e.status)
+    assert seen == FOREIGN_REJECTED
+
+
+def _scan_of(data):
+    """(first byte of the scan, offset of EOI) by a marker walk of the test's own: the window cases have neither fill bytes nor bytes
+    behind EOI."""
+    p = 2
+    while data[p + 1] != 0xDA:
+        p += 2 + ((data[p + 2] << 8) | data[p + 3])
+    assert data[-2:] == b"\xff\xd9"
+    return p + 2 + ((data[p + 2] << 8) | data[p + 3]), len(data) - 2
+
+
+def test_window_cases_lie_where_their_names_say():
+    """The window rule (jpeg_window.window_starts) on hand-made positions, and the committed window cases against it, from the files'
+    own bytes: the generator asserts the same from the writer's offsets when it makes them."""
+    assert window_starts([150]) == [144] and window_starts([150, 1168, 1169, 2300]) == [144, 144, 1168, 2288]
+    assert window_starts([0, HALF, HALF + 1, 2 * HALF + 1, 2 * HALF + 2]) == [0, 0, HALF, 2 * HALF, 2 * HALF]       # '>' HALF, not '>='
+    by_name = {c.name: c for c in FOREIGN}
+    a, e = _scan_of(by_name["win_dense_8"].data)
+    assert e - (a & ~(LINE - 1)) > WIN + LINE
+    for p in range(16):
+        d = by_name["win_ff00_end_p%02d" % p].data
+        a, e = _scan_of(d)
+        end = (a & ~(LINE - 1)) + WIN
+        assert a % LINE == p and end < e and d[end - 1:end + 1] == b"\xff\x00", p
+    for p in range(13):                                 # 13 .. 15 cannot be: the marker's two bytes, then a first byte that is never FF
+        d = by_name["win_ff00_line_p%02d" % p].data
+        a, e = _scan_of(d)
+        s1 = d.index(b"\xff\xd0", a)                      # the only marker of the scan: 16 blocks, restart interval 8
+        st = window_starts([a, s1])
+        assert s1 % LINE == p and st[1] == s1 & ~(LINE - 1) and st[1] != st[0] and d[st[1] + LINE - 1:st[1] + LINE + 1] == b"\xff\x00", p
+    phases, straddles = set(), 0
+    for c in (0, 5, 10, 15):
+        d = by_name["win_rst_shift%02d" % c].data
+        a, e = _scan_of(d)
+        rst = [k for k in range(a, e) if d[k] == 0xFF and 0xD0 <= d[k + 1] <= 0xD7]
+        assert len(rst) == 63 and [d[k + 1] - 0xD0 for k in rst] == [k & 7 for k in range(63)]
+        phases |= {k % LINE for k in rst}
+        starts = window_starts([a] + [rst[8 * g - 1] for g in range(1, 8)])
+        straddles += sum(r == starts[(k + 1) // 8] + WIN - 1 for k, r in enumerate(rst))
+    assert phases == set(range(LINE)) and straddles >= 1
+
+
+def test_writer_round_trip_and_offsets():
+    """tests/jpeg_writer.py against the restatement's reader: the coefficients that went in come out dequantised, block by block, and
+    the offsets it reports are those of the blocks' first bytes and of the RSTn markers."""
+    rng = np.random.default_rng(5)
+    quant = {0: [3 + k % 7 for k in range(64)], 1: [2 + k % 5 for k in range(64)]}
+    for (hs, vs), ri in (((1, 1), None), ((2, 1), 2), ((2, 2), 1)):
+        w, h = 37, 21
+        mx, my = -(-w // (8 * hs)), -(-h // (8 * vs))
+        coefs = [rng.integers(-9, 10, s + (64,)) * (rng.random(s + (64,)) < 0.3) for s in ((my * vs, mx * hs), (my, mx), (my, mx))]
+        coefs[0][0, 0, 1:] = 0
+        coefs[0][0, 0, 63] = 5                                      # three ZRLs, a run of 14, no EOB
+        wr = W.write(w, h, coefs, sampling=(hs, vs), quant=quant, restart=ri, pre_sof=[W.jfif()])
+        q, huff, ri2, sof, sel, pos, jfif, adobe = R._header(wr.data)
+        assert pos == wr.scan_off and ri2 == (ri or 0) and jfif and adobe is None and (sof["w"], sof["h"]) == (w, h)
+        blocks = []
+        R._scan(wr.data, pos, q, huff, ri2, sof["comps"], sel, hs, vs, mx, mx * my, None, blocks)
+        assert len(blocks) == len(wr.block_off) == mx * my * (hs * vs + 2)
+        for c, bx, by, coef in blocks:
+            want = np.zeros(64, dtype=np.int64)
+            want[R.ZIGZAG] = coefs[c][by, bx] * np.array(quant[min(c, 1)])
+            assert np.array_equal(np.array(coef), want), (hs, vs, c, bx, by)
+        assert wr.block_off[0] == wr.scan_off and all(a <= b for a, b in zip(wr.block_off, wr.block_off[1:]))
+        assert wr.data[wr.scan_end:wr.scan_end + 2] == b"\xff\xd9" and len(wr.rst_off) == ((mx * my - 1) // ri if ri else 0)
+        for k, o in enumerate(wr.rst_off):
+            assert wr.data[o] == 0xFF and wr.data[o + 1] == 0xD0 + (k & 7)
+            assert o + 2 in wr.block_off                            # the next block starts behind the marker
+
+
 def test_parser_info_and_reason_codes():
     from scd_amd import jpeg
-    for c in CASES:
+    for c in CASES + FOREIGN:
         i = jpeg.jpeg_info(c.data)
         assert i["reason"] == c.reason, (c.name, i)
         if c.reason != 0:
@@ -66,7 +185,7 @@ def test_parser_info_and_reason_codes():
 
 def test_host_decode_equals_pillow_golden():
     from scd_amd import jpeg
-    for c in ACCEPTED:
+    for c in ACCEPTED + FOREIGN_ACCEPTED:
         check_pixels(c, jpeg.decode_jpeg_host(c.data))
 
 
@@ -167,18 +286,25 @@ def test_host_decode_equals_installed_pillow_on_fresh_files():
 
 def test_restatement_equals_golden_and_library():
     from scd_amd import jpeg
-    for c in ACCEPTED:
+    for c in ACCEPTED + FOREIGN_ACCEPTED:
         ref = R.decode(c.data)
         check_pixels(c, ref)
         assert np.array_equal(ref, jpeg.decode_jpeg_host(c.data)), c.name
+
+
+PILLOW_WRITTEN_PLANTS = ("replicate", "swap_rounding", "unclamped_row", "padded_last_col", "clamp_range", "restart_keeps_pred")
 
 
 @pytest.mark.parametrize("plant", [p for p in R.PLANTS if p != "clamp_range"])
 def test_planted_mistake_changes_a_fixture_pixel(plant):
     """One rule of the restatement broken at a time (replication for fancy upsampling, the rounding terms swapped, the neighbour chroma
     row taken from the padding, the last column taken from the padded width, restarts that keep the DC predictors): every one must
-    change a pixel of an accepted fixture, or the fixtures do not pin that rule."""
-    hits = [c.name for c in ACCEPTED if c.w <= 64 and not np.array_equal(R.decode(c.data, plant=plant, guard=False), c.pixels)]
+    change a pixel of an accepted fixture, or the fixtures do not pin that rule.  Those six must be caught by the files Pillow's encoder
+    wrote alone.  The others are about what only other encoders write, and must be caught by the second file: an Adobe transform 0
+    beside JFIF taken for RGB, MCU geometry taken from a one-component frame's sampling factors, the first of two definitions of a table
+    or of the restart interval kept, a ZRL that advances 15, pad bits that must be ones, a table id taken & 1."""
+    cases = ACCEPTED if plant in PILLOW_WRITTEN_PLANTS else FOREIGN_ACCEPTED
+    hits = [c.name for c in cases if c.pixels is not None and not np.array_equal(R.decode(c.data, plant=plant, guard=False), c.pixels)]
     assert hits, plant
 
 
@@ -225,7 +351,7 @@ def test_range_guard_bounds():
 
 def test_host_code_under_sanitizers(tmp_path):
     """tests/sanitize_jpeg.cpp: the parser, the table builder and the CPU decoder under AddressSanitizer + UndefinedBehaviorSanitizer
-    over every fixture and 1,000 seeded corruptions, as a stand-alone program."""
+    over every fixture of both files and 1,000 seeded corruptions, as a stand-alone program."""
     clang = "/opt/rocm/lib/llvm/bin/clang++"
     if not os.path.exists(clang):
         clang = shutil.which("clang++")
@@ -236,5 +362,6 @@ def test_host_code_under_sanitizers(tmp_path):
            "-fno-omit-frame-pointer", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include", "-I", os.path.join(ROOT, "include"), "-I", src,
            os.path.join(src, "jpeg.hip"), os.path.join(ROOT, "tests", "sanitize_jpeg.cpp"), "-o", exe]
     subprocess.run(cmd, check=True, timeout=600)
-    r = subprocess.run([exe, GOLDEN], capture_output=True, text=True, timeout=600)
+    r = subprocess.run([exe, GOLDEN, GOLDEN_FOREIGN], capture_output=True, text=True, timeout=600)
+    assert "%d fixtures" % (len(CASES) + len(FOREIGN)) in r.stdout, r.stdout
     assert r.returncode == 0 and " 0 failures" in r.stdout and "runtime error" not in r.stderr and "Sanitizer" not in r.stderr, r.stdout + r.stderr
