@@ -456,6 +456,45 @@ int scd_knn(scd_handle h, const float* Q, int64_t m, const float* X, int64_t n, 
 int scd_knn_vote(scd_handle h, const int32_t* idx, const double* dot, int64_t m, int k_stride, int k_use, const int32_t* base_labels,
                  int64_t n, int mode, double temperature, int32_t* pred_out, double* score_out, void* stream);
 
+/* ---- exact t-SNE: scikit-learn 1.7's TSNE(n_components=2) as the reference's save_tsne / save_tsne_wcolor call it
+ *      (local_utils/util.py:178-216), with the exact all-pairs gradient instead of Barnes-Hut's (docs/design/tsne.md) ---- */
+/* The conditional affinities of a k-NN graph: dist2 double [n, k] (squared distances, finite and >= 0), row i ->
+ * p_out[i, j] = exp(-b_i (d_ij - d_i,min)) / sum, b_i (beta_out double [n]) the root of H_i(b) = log(perplexity), natural logarithms,
+ * all in float64.  The search is sklearn/manifold/_utils.pyx's: from b = 1, doubling or halving until the root is bracketed, then
+ * bisection - but with a fixed count of 200 steps and no exit on a tolerance, so the row is a function of the root alone.
+ * info_out int32 [2] = {rows whose entropy cannot reach the target (for example all k distances equal): they end at the last bracket
+ * value and still sum to 1; rows with a negative or non-finite distance: they get 1 / k and beta NaN}.
+ * Limits: 1 <= n < 2^31, 2 <= k <= 64, 1 < perplexity < k (SCD_EINVAL outside).  Two calls return the same bits. */
+int scd_tsne_calibrate(scd_handle h, const double* dist2, int64_t n, int k, double perplexity, double* p_out, double* beta_out,
+                       int32_t* info_out, void* stream);
+/* The gradient of KL(P || Q) at Y float [n, 2] (8-byte aligned) for the symmetric joint affinities P in CSR form (indptr int64 [n + 1],
+ * indices int32 [nnz], values double [nnz]):  q_ij = 1 / (1 + |y_i - y_j|^2),  Z = sum over i != j of q_ij,
+ *   grad_i = 4 [ exaggeration * sum_j P_ij q_ij (y_i - y_j) - (1 / Z) sum_{j != i} q_ij^2 (y_i - y_j) ]          (grad_out double [n, 2])
+ *   KL = sum over P_ij > 0 of P_ij log(P_ij Z / q_ij), always at exaggeration 1                                   (kl_out double [1], or NULL)
+ * and z_out double [1] = Z.  The all-pairs sums take each pair in fp32 (v_rcp_f32 for q) and fold runs of 64 columns into float64:
+ * per row |error| <= 80 * 2^-24 * the sum of the terms' magnitudes (docs/design/tsne.md); the pair i = i and the padding are excluded
+ * by index, coincident points count 1 in Z.  flags = SCD_TSNE_EXACT_PAIRS takes the pairs in float64 with a division instead (the
+ * same kernel at the float64 rate): the KL a fit reports is computed so.  The CSR sums and KL are float64 throughout.  No floating-point atomics: column ranges
+ * are combined in a fixed order, and two calls return the same bits.
+ * info_out int32 [2] = {rows with an indptr pair outside 0 <= lo <= hi <= nnz or a column outside [0, n): such entries are skipped and
+ * never dereferenced; rows of Y that are not finite with |y| < 2^60}.  A call with info_out != {0, 0} has no meaning beyond that.
+ * Limits: 2 <= n < 2^31, 0 <= nnz < 2^40; scd_tsne_gradient_ws_bytes returns 0 outside them.  The workspace holds the per-range
+ * partial sums: 24 n bytes per column range (at most 32 ranges) + 56 n.  scd_tsne_row_tile / scd_tsne_col_chunk: the rows of a
+ * block and the columns staged at a time (the tests place their sizes around them). */
+size_t scd_tsne_gradient_ws_bytes(int64_t n, int64_t nnz);
+int scd_tsne_row_tile(void);
+int scd_tsne_col_chunk(void);
+#define SCD_TSNE_EXACT_PAIRS 1
+int scd_tsne_gradient(scd_handle h, const float* Y, const int64_t* indptr, const int32_t* indices, const double* values, int64_t n,
+                      int64_t nnz, double exaggeration, int flags, double* grad_out, double* z_out, double* kl_out, int32_t* info_out,
+                      void* ws, size_t ws_bytes, void* stream);
+/* One step of _gradient_descent (sklearn/manifold/_t_sne.py) on the 2 n elements of the float64 state, in place:
+ *   gains += 0.2 where vel * grad < 0, else gains *= 0.8; gains = max(gains, min_gain); vel = momentum * vel - learning_rate * (gains * grad);
+ *   Y64 += vel; Y32_out = Y64 rounded to nearest.  gg_out double [n, 2] (or NULL) = gains * grad, the vector whose norm the optimiser's
+ * min_grad_norm test reads.  Every operation is the IEEE float64 one (no contraction): the step equals numpy's bit for bit. */
+int scd_tsne_update(scd_handle h, const double* grad, double* Y64, double* vel, double* gains, float* Y32_out, int64_t n, double momentum,
+                    double learning_rate, double min_gain, double* gg_out, void* stream);
+
 /* ---- host solvers (CPU, synchronous) ---- */
 /* linear_assignment (gcd/project_utils/cluster_utils.py:234-493), same tie-breaking; pairs_out [min(n,m),2] sorted */
 int scd_munkres(const int64_t* cost, int n, int m, int64_t* pairs_out, int* n_pairs_out);

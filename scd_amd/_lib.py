@@ -146,6 +146,15 @@ SIGNATURES = {
     "scd_knn": (_i, [_vp, _vp, _i64, _vp, _i64, _i, _i, _i64, _vp, _vp, _vp, _vp, _sz, _vp]),
     # h, idx, dot, m, k_stride, k_use, base_labels, n, mode, temperature, pred_out, score_out, stream
     "scd_knn_vote": (_i, [_vp, _vp, _vp, _i64, _i, _i, _vp, _i64, _i, C.c_double, _vp, _vp, _vp]),
+    # h, dist2, n, k, perplexity, p_out, beta_out, info_out, stream
+    "scd_tsne_calibrate": (_i, [_vp, _vp, _i64, _i, C.c_double, _vp, _vp, _vp, _vp]),
+    "scd_tsne_gradient_ws_bytes": (_sz, [_i64, _i64]),
+    "scd_tsne_row_tile": (_i, []),
+    "scd_tsne_col_chunk": (_i, []),
+    # h, Y, indptr, indices, values, n, nnz, exaggeration, flags, grad_out, z_out, kl_out, info_out, ws, ws_bytes, stream
+    "scd_tsne_gradient": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, C.c_double, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    # h, grad, Y64, vel, gains, Y32_out, n, momentum, learning_rate, min_gain, gg_out, stream
+    "scd_tsne_update": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, C.c_double, C.c_double, C.c_double, _vp, _vp]),
     "scd_munkres": (_i, [_vp, _i, _i, _vp, C.POINTER(_i)]),
     "scd_munkres_sparse": (_i, [_i, _i64, _vp, _vp, _vp, _vp, C.POINTER(_i)]),
     "scd_transport_solve": (_i, [_vp, _i64, _i, _i, _i, _vp, C.POINTER(_i64)]),

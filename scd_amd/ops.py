@@ -1318,3 +1318,58 @@ class Encoder:
             check(_L().scd_clip_encode_text_len(handle(), self._enc, ptr(tokens), b, int(ctx_len), ptr(out), 1 if normalize else 0,
                                                 ptr(ws), nb, stream_ptr()))
         return out
+
+
+# ----------------------------------------------------------------------------- exact t-SNE (docs/design/tsne.md)
+def tsne_calibrate(dist2, perplexity):
+    """scd_tsne_calibrate: dist2 float64 [n, k] (squared distances of a k-NN graph) -> (p float64 [n, k], every row summing to 1,
+    beta float64 [n], info int32 [2] = rows whose entropy cannot reach log(perplexity), rows with a bad distance)."""
+    _need_cuda(dist2)
+    if dist2.dim() != 2 or dist2.dtype != torch.float64:
+        raise _lib.ScdError(_lib.SCD_EINVAL, "tsne_calibrate: dist2 must be float64 [n, k]")
+    dist2 = dist2.contiguous()
+    n, k = dist2.shape
+    p = torch.empty_like(dist2)
+    beta = torch.empty(n, dtype=torch.float64, device=dist2.device)
+    info = torch.empty(2, dtype=torch.int32, device=dist2.device)
+    check(_L().scd_tsne_calibrate(handle(), ptr(dist2), n, k, float(perplexity), ptr(p), ptr(beta), ptr(info), stream_ptr()))
+    return p, beta, info
+
+
+TSNE_EXACT_PAIRS = 1
+
+
+def tsne_gradient(y, indptr, indices, values, exaggeration=1.0, want_kl=True, ws=None, exact_pairs=False):
+    """scd_tsne_gradient: y float32 [n, 2], P in CSR form (indptr int64 [n + 1], indices int32 [nnz], values float64 [nnz]) ->
+    (grad float64 [n, 2], z float64 [1], kl float64 [1] or None, info int32 [2] = rows with an out-of-range CSR entry, rows of y that
+    are not finite below 2^60), on the device.  exact_pairs: the all-pairs sums in float64 instead of fp32 runs."""
+    _need_cuda(y, indptr, indices, values)
+    if (y.dim() != 2 or y.shape[1] != 2 or y.dtype != torch.float32 or indptr.dtype != torch.int64 or indices.dtype != torch.int32
+            or values.dtype != torch.float64 or indptr.numel() != y.shape[0] + 1 or indices.numel() != values.numel()):
+        raise _lib.ScdError(_lib.SCD_EINVAL, "tsne_gradient: y float32 [n, 2], indptr int64 [n + 1], indices int32 [nnz], values float64 [nnz]")
+    y, indptr, indices, values = y.contiguous(), indptr.contiguous(), indices.contiguous(), values.contiguous()
+    n, nnz = y.shape[0], indices.numel()
+    grad = torch.empty((n, 2), dtype=torch.float64, device=y.device)
+    z = torch.empty(1, dtype=torch.float64, device=y.device)
+    kl = torch.empty(1, dtype=torch.float64, device=y.device) if want_kl else None
+    info = torch.empty(2, dtype=torch.int32, device=y.device)
+    nb = _L().scd_tsne_gradient_ws_bytes(n, nnz)
+    if ws is None or ws.numel() < nb:
+        ws = _ws(max(nb, 16), y.device)
+    check(_L().scd_tsne_gradient(handle(), ptr(y), ptr(indptr), ptr(indices) if nnz else None, ptr(values) if nnz else None, n, nnz,
+                                 float(exaggeration), TSNE_EXACT_PAIRS if exact_pairs else 0, ptr(grad), ptr(z), ptr(kl) if want_kl else None, ptr(info), ptr(ws), nb, stream_ptr()))
+    return grad, z, kl, info
+
+
+def tsne_update(grad, y64, vel, gains, y32, momentum, learning_rate, min_gain=0.01, gg_out=None):
+    """scd_tsne_update: one _gradient_descent step on the float64 state (y64, vel, gains: [n, 2], updated in place) and the float32 copy
+    y32 the force kernels read; gg_out float64 [n, 2] (optional) receives gains * grad."""
+    _need_cuda(grad, y64, vel, gains, y32, gg_out)
+    n = y64.shape[0]
+    for t in (grad, y64, vel, gains) + (() if gg_out is None else (gg_out,)):
+        if t.dtype != torch.float64 or tuple(t.shape) != (n, 2) or not t.is_contiguous():
+            raise _lib.ScdError(_lib.SCD_EINVAL, "tsne_update: grad, y64, vel, gains (and gg_out) must be contiguous float64 [n, 2]")
+    if y32.dtype != torch.float32 or tuple(y32.shape) != (n, 2) or not y32.is_contiguous():
+        raise _lib.ScdError(_lib.SCD_EINVAL, "tsne_update: y32 must be contiguous float32 [n, 2]")
+    check(_L().scd_tsne_update(handle(), ptr(grad), ptr(y64), ptr(vel), ptr(gains), ptr(y32), n, float(momentum), float(learning_rate),
+                               float(min_gain), None if gg_out is None else ptr(gg_out), stream_ptr()))
