@@ -456,6 +456,37 @@ int scd_knn(scd_handle h, const float* Q, int64_t m, const float* X, int64_t n, 
 int scd_knn_vote(scd_handle h, const int32_t* idx, const double* dot, int64_t m, int k_stride, int k_use, const int32_t* base_labels,
                  int64_t n, int mode, double temperature, int32_t* pred_out, double* score_out, void* stream);
 
+/* ---- the linear probe: multinomial logistic regression on frozen features (the linear evaluation of DINO / DINOv2; scikit-learn's
+ *      LogisticRegression(C) written as a sum; the reference trains the same head in gcd/methods/cluster_and_classifier/
+ *      train_supervised.py; docs/design/probe.md) ---- */
+/* Bytes of workspace of scd_probe_loss_grad for X [n, d] and c classes: the packed W, the residuals r float32 [n, c up to 32], the row
+ * losses float32 [n] and the float64 partial sums of the row ranges; 0.65 GB at n = 126,976, d = 768, c = 1000.  0 outside the limits
+ * 1 <= n < 2^31, 1 <= d <= 1024, 2 <= c <= 1024.  scd_probe_predict needs scd_probe_ws_bytes(1, d, c) whatever its n. */
+size_t scd_probe_ws_bytes(int64_t n, int d, int c);
+/* Rows of X a block of the forward kernel owns (with all c classes). */
+int scd_probe_row_tile(void);
+/* The longest float32 accumulation chain over rows in the gradient (<= 1024): a chain's 32 x 32 tile is added into float64, so the
+ * gradient's rounding error is gamma_T sum_i |r_ic x_id| with T this value, whatever n. */
+int scd_probe_chain_rows(void);
+/* The data term of the objective and its gradient at (W, b):
+ *   loss = sum_i s_i [lse_c(z_ic) - z_{i,y_i}],  gW = r^T X,  gb = column sums of r,  z_ic = W_c . x_i + b_c,
+ *   r_ic = s_i (softmax(z_i)_c - [c == y_i]),  s_i = sample_weight[i], or 1 when sample_weight is NULL.
+ * X float32 [n, d], y int32 [n], W float32 [c, d], b float32 [c] or NULL (then b = 0); loss_out double [1], gW_out double [c, d], gb_out
+ * double [c] or NULL, pred_out int32 [n] or NULL: argmax_c z_ic, ties to the lowest class.  info_out int32 [2] = {rows whose label is
+ * outside [0, c): such a row contributes nothing, as if its weight were 0; rows with a non-finite logit: the outputs are then not
+ * meaningful}.  The logits are float32 fma chains over k ascending from zero (the float32-input MFMA), b added last; the softmax uses
+ * expf / logf and a correctly rounded division on z - max, the maximum over the real classes; the gradient accumulates float32 over
+ * chains of scd_probe_chain_rows() rows and float64 across them.  No [n, c] logits reach memory, only r.  The L2 term of the objective
+ * is the caller's.  Two calls return the same bits: no floating-point atomics, and every partition of the work depends on (n, d, c)
+ * alone. */
+int scd_probe_loss_grad(scd_handle h, const float* X, const int32_t* y, const float* sample_weight, int64_t n, int d, int c, const float* W,
+                        const float* b, double* loss_out, double* gW_out, double* gb_out, int32_t* pred_out, int32_t* info_out, void* ws,
+                        size_t ws_bytes, void* stream);
+/* The forward pass alone: pred_out int32 [n] = argmax_c z_ic (ties to the lowest class), the same logits as scd_probe_loss_grad's, and
+ * top_logit_out float32 [n, 2] or NULL: the largest and the second largest logit of the row (equal when two classes tie). */
+int scd_probe_predict(scd_handle h, const float* X, int64_t n, int d, int c, const float* W, const float* b, int32_t* pred_out,
+                      float* top_logit_out, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- exact t-SNE: scikit-learn 1.7's TSNE(n_components=2) as the reference's save_tsne / save_tsne_wcolor call it
  *      (local_utils/util.py:178-216), with the exact all-pairs gradient instead of Barnes-Hut's (docs/design/tsne.md) ---- */
 /* The conditional affinities of a k-NN graph: dist2 double [n, k] (squared distances, finite and >= 0), row i ->

@@ -146,6 +146,13 @@ SIGNATURES = {
     "scd_knn": (_i, [_vp, _vp, _i64, _vp, _i64, _i, _i, _i64, _vp, _vp, _vp, _vp, _sz, _vp]),
     # h, idx, dot, m, k_stride, k_use, base_labels, n, mode, temperature, pred_out, score_out, stream
     "scd_knn_vote": (_i, [_vp, _vp, _vp, _i64, _i, _i, _vp, _i64, _i, C.c_double, _vp, _vp, _vp]),
+    "scd_probe_ws_bytes": (_sz, [_i64, _i, _i]),
+    "scd_probe_row_tile": (_i, []),
+    "scd_probe_chain_rows": (_i, []),
+    # h, X, y, sample_weight, n, d, c, W, b, loss_out, gW_out, gb_out, pred_out, info_out, ws, ws_bytes, stream
+    "scd_probe_loss_grad": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    # h, X, n, d, c, W, b, pred_out, top_logit_out, ws, ws_bytes, stream
+    "scd_probe_predict": (_i, [_vp, _vp, _i64, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     # h, dist2, n, k, perplexity, p_out, beta_out, info_out, stream
     "scd_tsne_calibrate": (_i, [_vp, _vp, _i64, _i, C.c_double, _vp, _vp, _vp, _vp]),
     "scd_tsne_gradient_ws_bytes": (_sz, [_i64, _i64]),

@@ -997,6 +997,60 @@ def knn_vote(idx, dot, base_labels, k_use=None, mode=KNN_SOFTMAX, temperature=0.
     return pred, score
 
 
+# ----------------------------------------------------------------------------- the linear probe (docs/design/probe.md)
+def _probe_args(who, x, w, b):
+    _need_cuda(x, w)
+    if x.dim() != 2 or w.dim() != 2 or x.dtype != torch.float32 or w.dtype != torch.float32 or x.shape[1] != w.shape[1]:
+        raise _lib.ScdError(_lib.SCD_EINVAL, who + ": x float32 [n, d] and w float32 [c, d]")
+    if b is not None:
+        _need_cuda(b)
+        if b.dtype != torch.float32 or b.shape != (w.shape[0],):
+            raise _lib.ScdError(_lib.SCD_EINVAL, who + ": b float32 [c]")
+        b = b.contiguous()
+    return x.contiguous(), w.contiguous(), b
+
+
+def probe_loss_grad(x, y, w, b=None, sample_weight=None, want_pred=False):
+    """scd_probe_loss_grad: x float32 [n, d], y int32 [n], w float32 [c, d], b float32 [c] or None, sample_weight float32 [n] or None ->
+    (loss float64 [1], gw float64 [c, d], gb float64 [c] or None without b, pred int32 [n] or None, info int32 [2] = rows with a label
+    outside [0, c), rows with a non-finite logit), all on the device.  The data term sum_i s_i [lse(z_i) - z_{i, y_i}] of multinomial
+    logistic regression and its gradient; the L2 term is the caller's."""
+    x, w, b = _probe_args("probe_loss_grad", x, w, b)
+    _need_cuda(y)
+    (n, d), c = x.shape, w.shape[0]
+    if y.dtype != torch.int32 or y.shape != (n,):
+        raise _lib.ScdError(_lib.SCD_EINVAL, "probe_loss_grad: y int32 [n]")
+    y = y.contiguous()
+    if sample_weight is not None:
+        _need_cuda(sample_weight)
+        if sample_weight.dtype != torch.float32 or sample_weight.shape != (n,):
+            raise _lib.ScdError(_lib.SCD_EINVAL, "probe_loss_grad: sample_weight float32 [n]")
+        sample_weight = sample_weight.contiguous()
+    loss = torch.empty(1, dtype=torch.float64, device=x.device)
+    gw = torch.empty((c, d), dtype=torch.float64, device=x.device)
+    gb = torch.empty(c, dtype=torch.float64, device=x.device) if b is not None else None
+    pred = torch.empty(n, dtype=torch.int32, device=x.device) if want_pred else None
+    info = torch.empty(2, dtype=torch.int32, device=x.device)
+    nb = _L().scd_probe_ws_bytes(n, d, c)
+    ws = _ws(max(nb, 16), x.device)
+    check(_L().scd_probe_loss_grad(handle(), ptr(x), ptr(y), ptr(sample_weight), n, d, c, ptr(w), ptr(b), ptr(loss), ptr(gw), ptr(gb),
+                                   ptr(pred), ptr(info), ptr(ws), nb, stream_ptr()))
+    return loss, gw, gb, pred, info
+
+
+def probe_predict(x, w, b=None, want_top=False):
+    """scd_probe_predict: x float32 [n, d], w float32 [c, d], b float32 [c] or None -> pred int32 [n] = argmax_c (w_c . x_i + b_c), ties to
+    the lowest class; with want_top also top float32 [n, 2], the largest and second largest logit of each row."""
+    x, w, b = _probe_args("probe_predict", x, w, b)
+    (n, d), c = x.shape, w.shape[0]
+    pred = torch.empty(n, dtype=torch.int32, device=x.device)
+    top = torch.empty((n, 2), dtype=torch.float32, device=x.device) if want_top else None
+    nb = _L().scd_probe_ws_bytes(1, d, c)
+    ws = _ws(max(nb, 16), x.device)
+    check(_L().scd_probe_predict(handle(), ptr(x), n, d, c, ptr(w), ptr(b), ptr(pred), ptr(top), ptr(ws), nb, stream_ptr()))
+    return (pred, top) if want_top else pred
+
+
 # ----------------------------------------------------------------------------- host solvers
 def munkres(cost):
     """linear_assignment (cluster_utils.py:234): int array [n,m] -> sorted pairs [min(n,m),2]."""
