@@ -558,6 +558,33 @@ int scd_comm_destroy(scd_handle h);
 int scd_allreduce_centroids(scd_handle h, double* packed, int64_t count, void* stream);
 int scd_allgather_text(scd_handle h, const void* w_shard, int64_t shard_elems, void* w_full, void* stream);
 
+/* ---- spectral clustering on the exact k-NN graph: scikit-learn 1.7's SpectralClustering(affinity='nearest_neighbors')
+ *      (sklearn/cluster/_spectral.py:_fit; no counterpart in the reference; docs/design/spectral.md) ---- */
+/* The symmetric normalised affinity of k-NN lists, in CSR form.  idx int32 [n][k] (scd_knn's idx_out: a row does not list itself; k =
+ * scikit-learn's n_neighbors - 1).  Replaces sklearn.neighbors.kneighbors_graph(include_self=True) + `0.5 * (C + C.T)`
+ * (sklearn/cluster/_spectral.py) and scipy.sparse.csgraph.laplacian(normed=True)'s `w = sqrt(degree); m /= w; m /= w[:, None]`
+ * (scipy/sparse/csgraph/_laplacian.py) with the diagonal removed first (sklearn/manifold/_spectral_embedding.py):
+ *   A[i][j] = 1 when i and j list each other, 0.5 when one lists the other;  d_i = sum_j A[i][j] (a multiple of 0.5, exact);
+ *   S[i][j] = A[i][j] / (sqrt(d_i) * sqrt(d_j)) in float64, these operations in this order: S is symmetric bit for bit.
+ * A negative entry and idx[i][j] == i are ignored, a neighbour listed twice in a row counts once, an index >= n is SCD_EINVAL.
+ * rowptr int64 [n + 1], col int32 [cap] and val double [cap] with cap >= 2 n k; columns ascend inside a row, so the result is one fixed
+ * array; *nnz_out (host) = rowptr[n].  inv_sqrt_deg double [n] = 1 / sqrt(d_i), and 1 for a row without an edge (scipy's isolated
+ * nodes).  A row's length is its list plus its one-way in-degree: nothing is sized by 2 k.  The call waits for the stream (the index
+ * check and nnz come back to the host).  Limits: 2 <= n < 2^31, 1 <= k <= 64; scd_knn_affinity_ws_bytes returns 0 outside them. */
+size_t scd_knn_affinity_ws_bytes(int64_t n, int k);
+int scd_knn_affinity(scd_handle h, const int32_t* idx, int64_t n, int k, int64_t* rowptr, int32_t* col, double* val, double* inv_sqrt_deg,
+                     int64_t cap, int64_t* nnz_out, void* ws, size_t ws_bytes, void* stream);
+/* Y = alpha (S X) + beta X + gamma Z for S in CSR form (n rows and columns) and blocks X [n][ldx], Z [n][ldz] (or NULL: no third term),
+ * Y [n][ldy] of m columns, float64: the sparse product of scipy.sparse's `S @ X` under sklearn's eigensolver, and one step of the
+ * Chebyshev three-term recurrence in one launch.  The summation order is part of the contract: a row of at most 512 entries is summed
+ * left to right in CSR order from 0, a multiply and an add per term, no fused multiply-add; a longer row is cut into chunks of 512
+ * entries, each summed that way, and the chunk sums are added in chunk order from 0; then (alpha * sum + beta * x) + gamma * z.  No
+ * floating-point atomics: two calls return the same bits, and numpy can restate them.  A column outside [0, n) reads nothing and
+ * counts as a row of zeros; a row pointer pair outside 0 <= lo <= hi <= rowptr[n] makes an empty row.
+ * Limits: m % 8 == 0, leading dimensions multiples of 8 and >= m, blocks 16-byte aligned, Y's span overlaps neither X's nor Z's. */
+int scd_spmm_f64(scd_handle h, const int64_t* rowptr, const int32_t* col, const double* val, int64_t n, const double* X, int64_t ldx, int m,
+                 double alpha, double beta, double gamma, const double* Z, int64_t ldz, double* Y, int64_t ldy, void* stream);
+
 /* ---- encoders: CLIP ViT-B/16 visual / text (third-party `clip`, call sites main_unsup.py:127,
  *      clip_lang_util.py:101-102), DINO ViT-B/16 (gcd/models/vision_transformer.py:135-219) and DINOv2 ViT-B/14 / ViT-L/14 with or
  *      without register tokens (kind 2 with patch 14; LayerScale, the position table at 16 x 16 and the input normalisation are

@@ -7,6 +7,7 @@ Here every stage starts from the reference's own cache files under --root_dir, b
   extracted_features/{feat_model}_{dataset}_all.pt   dict all_feats, mask_lab, mask_cls, targets      (:141-146,294-301)
   extracted_features/clip_{dataset}_all.pt           same dict, CLIP features                          (:306-311)
   cluster/{cluster}_{feat_model}_{dataset}_{n_cluster}.pt   dict all_preds, u_preds, u_targets, mask  (:366-374)
+                                                            ({cluster} = KM, SSKM, ConSSKM, FINCH or SC)
   zeroshot_weights/zeroshot_weights_all_{nouns|wikibird|wikidog}_vit_b_16.pt   tensor [512, V]        (:389-394)
 --clip_model picks the CLIP backbone (clip.available_models(), default ViT-B/16: the names above).  With another one every
 CLIP-derived cache carries its tag, so that no cache of one backbone is read as another's features:
@@ -60,9 +61,12 @@ def build_parser():
     p.add_argument('--transform', type=str, default='imagenet')
     p.add_argument('--extract_feat', type=str2bool, default=False)
     p.add_argument('--run_cluster', type=str2bool, default=False)
-    p.add_argument('--cluster', type=str, default='KM', help='options: KM, SSKM, ConSSKM, FINCH (first-neighbour clustering refined to --n_cluster clusters)')
+    p.add_argument('--cluster', type=str, default='KM', help='options: KM, SSKM, ConSSKM, FINCH (first-neighbour clustering refined to --n_cluster clusters), '
+                                                                     'SC (spectral clustering on the exact k-NN graph, see --n_neighbors)')
     p.add_argument('--save_cluster', type=str2bool, default=False)
     p.add_argument('--n_cluster', type=int, default=1000)
+    p.add_argument('--n_neighbors', type=int, default=10,
+                   help="--cluster SC: neighbours per row of the graph, the row itself included (scikit-learn's n_neighbors), 2 to 65")
     p.add_argument('--cluster_size_min', type=int, default=50)
     p.add_argument('--cluster_size_max', type=int, default=1200)
     p.add_argument('--corpus', type=str, default='wordnet', help='options: wordnet, wikibird, wikidog')
@@ -99,6 +103,12 @@ def run_clustering(args, u_feats, l_feats, l_targets):
         from scd_amd.local_utils.finch import FINCH
         _, _, req_c = FINCH(np.asarray(u_feats, dtype=np.float32), req_clust=args.n_cluster, verbose=True)
         return None, req_c.astype(np.int64)
+    elif args.cluster == 'SC':
+        # sklearn's SpectralClustering(n_clusters, affinity='nearest_neighbors', n_neighbors, random_state=0) on the unlabelled rows: the
+        # k-NN graph, its normalised affinity and the eigensolver's sparse products on the device (docs/design/spectral.md)
+        from scd_amd.spectral import SpectralClustering
+        sc = SpectralClustering(n_clusters=args.n_cluster, n_neighbors=args.n_neighbors, random_state=0)
+        return None, sc.fit_predict(np.asarray(u_feats, dtype=np.float32)).astype(np.int64)
     else:
         raise NotImplementedError(args.cluster)
     u, l, lt = (torch.as_tensor(x).to(dev) for x in (u_feats, l_feats, l_targets))

@@ -162,6 +162,11 @@ SIGNATURES = {
     "scd_tsne_gradient": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, C.c_double, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     # h, grad, Y64, vel, gains, Y32_out, n, momentum, learning_rate, min_gain, gg_out, stream
     "scd_tsne_update": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, C.c_double, C.c_double, C.c_double, _vp, _vp]),
+    "scd_knn_affinity_ws_bytes": (_sz, [_i64, _i]),
+    # h, idx, n, k, rowptr, col, val, inv_sqrt_deg, cap, nnz_out (host int64), ws, ws_bytes, stream
+    "scd_knn_affinity": (_i, [_vp, _vp, _i64, _i, _vp, _vp, _vp, _vp, _i64, C.POINTER(_i64), _vp, _sz, _vp]),
+    # h, rowptr, col, val, n, X, ldx, m, alpha, beta, gamma, Z, ldz, Y, ldy, stream
+    "scd_spmm_f64": (_i, [_vp, _vp, _vp, _vp, _i64, _vp, _i64, _i, C.c_double, C.c_double, C.c_double, _vp, _i64, _vp, _i64, _vp]),
     "scd_munkres": (_i, [_vp, _i, _i, _vp, C.POINTER(_i)]),
     "scd_munkres_sparse": (_i, [_i, _i64, _vp, _vp, _vp, _vp, C.POINTER(_i)]),
     "scd_transport_solve": (_i, [_vp, _i64, _i, _i, _i, _vp, C.POINTER(_i64)]),

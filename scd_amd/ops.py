@@ -1427,3 +1427,45 @@ def tsne_update(grad, y64, vel, gains, y32, momentum, learning_rate, min_gain=0.
         raise _lib.ScdError(_lib.SCD_EINVAL, "tsne_update: y32 must be contiguous float32 [n, 2]")
     check(_L().scd_tsne_update(handle(), ptr(grad), ptr(y64), ptr(vel), ptr(gains), ptr(y32), n, float(momentum), float(learning_rate),
                                float(min_gain), None if gg_out is None else ptr(gg_out), stream_ptr()))
+
+
+# ----------------------------------------------------------------------------- spectral clustering's sparse half (docs/design/spectral.md)
+def knn_affinity(idx, cap=None):
+    """scd_knn_affinity: idx int32 [n, k] (ops.knn's lists) -> (rowptr int64 [n + 1], col int32 [nnz], val float64 [nnz], inv_sqrt_deg
+    float64 [n], nnz), the symmetric normalised affinity S = D^-1/2 (0.5 (C + C^T)) D^-1/2 in CSR form with ascending columns.  cap: the
+    capacity handed to the library (default 2 n k, its minimum).  Waits for the stream."""
+    _need_cuda(idx)
+    if idx.dim() != 2 or idx.dtype != torch.int32:
+        raise _lib.ScdError(_lib.SCD_EINVAL, "knn_affinity: idx must be int32 [n, k]")
+    idx = idx.contiguous()
+    n, k = idx.shape
+    cap = 2 * n * k if cap is None else int(cap)
+    rowptr = torch.empty(n + 1, dtype=torch.int64, device=idx.device)
+    col = torch.empty(max(cap, 1), dtype=torch.int32, device=idx.device)
+    val = torch.empty(max(cap, 1), dtype=torch.float64, device=idx.device)
+    isd = torch.empty(n, dtype=torch.float64, device=idx.device)
+    nb = _L().scd_knn_affinity_ws_bytes(n, k)
+    ws = _ws(max(nb, 16), idx.device)
+    nnz = C.c_int64(0)
+    check(_L().scd_knn_affinity(handle(), ptr(idx), n, k, ptr(rowptr), ptr(col), ptr(val), ptr(isd), cap, C.byref(nnz), ptr(ws), nb, stream_ptr()))
+    nnz = int(nnz.value)
+    return rowptr, col[:nnz], val[:nnz], isd, nnz
+
+
+def spmm_f64(rowptr, col, val, x, alpha=1.0, beta=0.0, gamma=0.0, z=None, out=None):
+    """scd_spmm_f64: out = alpha (S x) + beta x + gamma z for S in CSR form (rowptr int64 [n + 1], col int32, val float64) and float64
+    blocks x, z, out [n, m] with unit column stride (a column slice of a wider buffer is fine: its row stride is the leading dimension).
+    m % 8 == 0, row strides multiples of 8; out may alias neither x nor z.  The summation order is fixed (include/scd_hip.h)."""
+    _need_cuda(x, rowptr, col, val, z, out)
+    n = rowptr.numel() - 1
+    if rowptr.dtype != torch.int64 or col.dtype != torch.int32 or val.dtype != torch.float64 or col.numel() != val.numel():
+        raise _lib.ScdError(_lib.SCD_EINVAL, "spmm_f64: rowptr int64 [n + 1], col int32 [nnz], val float64 [nnz]")
+    if out is None:
+        out = torch.empty((n, x.shape[1] if x.dim() == 2 else 0), dtype=torch.float64, device=x.device)
+    for name, t in (("x", x), ("z", z), ("out", out)):
+        if t is not None and (t.dim() != 2 or t.dtype != torch.float64 or t.shape != x.shape or t.shape[0] != n or t.stride(1) != 1):
+            raise _lib.ScdError(_lib.SCD_EINVAL, "spmm_f64: %s must be float64 [n = %d, m] with unit column stride" % (name, n))
+    rowptr, col, val = rowptr.contiguous(), col.contiguous(), val.contiguous()
+    check(_L().scd_spmm_f64(handle(), ptr(rowptr), ptr(col), ptr(val), n, ptr(x), x.stride(0), x.shape[1], float(alpha), float(beta), float(gamma),
+                            None if z is None else ptr(z), 0 if z is None else z.stride(0), ptr(out), out.stride(0), stream_ptr()))
+    return out
