@@ -1,5 +1,5 @@
 """A numpy float64 restatement of scd_knn / scd_knn_vote (include/scd_hip.h, docs/design/knn.md), the named cases of the k-NN tests,
-planted mistakes, and a CPU simulation of the fp16 filter that says how many candidates each row gets.
+planted mistakes, and a CPU simulation of the fp16 filter that says how many candidates each row gets (on exact-grid rows: exactly).
 
 The value of a pair is fn_dot64's: element c goes into partial sum c mod 4 in increasing c, then (s0 + s1) + (s2 + s3).  The product of two
 float32 values is exact in float64, so `s += a * b` in float64 IS the kernel's fma, and `dot64` returns the device's bits."""
@@ -11,6 +11,12 @@ from oracle import synth
 MISTAKES = ("self", "tie_high", "k_minus_1", "unsorted", "vote_tie_high", "no_temperature", "shard_base")
 KNN_MISTAKES = ("self", "tie_high", "k_minus_1", "unsorted", "shard_base")
 VOTE_MISTAKES = ("vote_tie_high", "no_temperature")
+# mistakes of one code path each, shown on the cases named for that path (tests/test_knn_host.py): only the first tile of a range is seen,
+# the exact pass keeps the best of its first chunk, the padding columns of the last tile are admitted with dot 0, the self column is
+# admitted with value 0 (the exact pass's placeholder entry)
+PATH_MISTAKES = ("first_tile_only", "first_chunk_only", "pad_cols", "self_zero")
+TILE = 128              # KNN_BN: columns per tile of the two MFMA passes
+CHUNK = 448             # KNN_SLOTS - KNN_KMAX: columns per step of the exact pass
 
 
 # ---------------------------------------------------------------------------------------------------- the value of a pair
@@ -28,13 +34,21 @@ def knn_f64(q, x, k, self_base=-1, mistake=None):
     column ascending).  A BLAS float64 product only shortlists: every column within 1e-11 |q_i| max|x_j| of the k-th largest BLAS value -
     a hundred times the error of any summation order - gets its dot64, and those decide."""
     q, x = np.ascontiguousarray(q, dtype=np.float32), np.ascontiguousarray(x, dtype=np.float32)
+    if mistake == "pad_cols":                                   # the zero rows that fill the last tile count as columns
+        x = np.concatenate([x, np.zeros((-x.shape[0] % TILE, x.shape[1]), dtype=np.float32)])
     m, n = q.shape[0], x.shape[0]
     q64, x64 = q.astype(np.float64), x.astype(np.float64)
     g = q64 @ x64.T
     tol = 1e-11 * np.sqrt((q64 * q64).sum(1)) * np.sqrt((x64 * x64).sum(1)).max() + 1e-300
-    if self_base >= 0 and mistake != "self":
+    if self_base >= 0 and mistake == "self_zero":
+        g[np.arange(m), self_base + np.arange(m)] = 0.0
+    elif self_base >= 0 and mistake != "self":
         base = 0 if mistake == "shard_base" else self_base
         g[np.arange(m), base + np.arange(m)] = -np.inf
+    if mistake == "first_tile_only":
+        g[:, (np.arange(n) // TILE) % ranges(m, n, k)[1] != 0] = -np.inf
+    if mistake == "first_chunk_only":
+        g[:, CHUNK:] = -np.inf
     need = k + 1 if mistake == "k_minus_1" else k
     idx, dot = np.zeros((m, k), dtype=np.int64), np.zeros((m, k))
     cands, wants = [], []
@@ -48,6 +62,8 @@ def knn_f64(q, x, k, self_base=-1, mistake=None):
         wants.append(want)
     rows, cols = np.repeat(np.arange(m), [len(c) for c in cands]), np.concatenate(cands)
     vals = np.concatenate([dot64(q[rows[s:s + 16384]], x[cols[s:s + 16384]]) for s in range(0, len(rows), 16384)])
+    if self_base >= 0 and mistake == "self_zero":
+        vals[cols == self_base + rows] = 0.0
     ends = np.cumsum([len(c) for c in cands])
     for i in range(m):
         cand, v, want = cands[i], vals[ends[i] - len(cands[i]):ends[i]], wants[i]
@@ -181,6 +197,78 @@ def blob_case(name):
     return case
 
 
+# ---------------------------------------------------------------------------------------------------- the paths that need n > 4096
+# More than 32 tiles, so that a range of the two MFMA passes holds several tiles on a device of any size (ranges(), asserted for 64, 256
+# and 304 compute units in tests/test_knn_host.py).  The seeds are chosen so that the facts the host test asserts of each case hold.
+BORDER = (4000, 4260)                                          # self columns in tiles 31, 32 and 33; tile 33 is the second of its range
+
+
+def tile_cases():
+    out = {}
+    x, q = _rand(100, 4097, 33), _rand(101, 129, 33)           # 33 tiles, 17 ranges of 2; the last range: one tile with ONE valid column
+    x[4096], x[4095] = 2 * q[5], 2 * q[77]                     # column 4096 is query 5's first neighbour
+    out["t33_q129"] = _case(x, 17, -1, q=q)
+    out["t65_q129"] = _case(_rand(102, 8200, 64), 16, -1, q=_rand(103, 129, 64))           # 65 tiles, 22 ranges of 3, the last clipped to 2
+    out["t34_k64"] = _case(_rand(104, 4225, 40), 64, -1, q=_rand(105, 260, 40))            # k / 4 = 16 ranges wanted, 17 of 2 tiles given
+    x = _grid(106, 4300, 64, amp=4, step=2.0 ** -3)            # dots are multiples of 2^-6 below 16: exact in fp32 in any order, many ties
+    out["border_shard"] = _case(x, 12, BORDER[0], q=x[BORDER[0]:BORDER[1]])
+    out["graph_4225"] = _case(_rand(107, 4225, 32), 20, 0)     # Q is X: 34 panels x 17 ranges of 2, one preparation for both sides
+    return out
+
+
+def _flagged(seed, n):
+    x = _rand(seed, n, 24)
+    x[n // 3, 3] = 131072.0                                     # does not fit fp16: the flag, every row through the exact pass
+    return _case(x, 64, 0)
+
+
+# name -> seed of the flagged cases: n = 3 chunks + ONE column, an exact multiple of the chunk, one past a chunk
+FLAGGED = {"flagged_1345_k64": (110, 1345), "flagged_896": (111, 896), "flagged_449": (112, 449)}
+
+
+def chunk_cases():
+    """The exact pass over several chunks of CHUNK columns with distinct values: a later chunk changes the best so far."""
+    out = {}
+    x = _rand(108, 4200, 64)
+    x[4150] *= 3000.0                                           # max |x| of some thousands fits fp16, but h_max makes every bound huge
+    out["hub"] = _case(x, 10, 0, m=200)
+    x = (8.0 + 2.0 ** -6 * np.random.RandomState(146).randn(4200, 64)).astype(np.float32)  # same-sign rows, near-ties far below fp16 resolution
+    out["offset"] = _case(x, 10, 0, m=200)
+    for name, (seed, n) in FLAGGED.items():
+        out[name] = _flagged(seed, n)
+    return out
+
+
+def chunks_of(case):
+    return -(-case["x"].shape[0] // CHUNK)
+
+
+def simplex_rows(n=120, d=128):
+    """Rows e_i - 1 / d: every pair's dot is exactly -1 / d (d a power of two), every value fits fp16."""
+    x = np.full((n, d), -1.0 / d, dtype=np.float32)
+    x[np.arange(n), np.arange(n)] += 1.0
+    return x
+
+
+def negative_cases():
+    """Every admissible dot is negative: a padding column (approximate dot 0) or the exact pass's self entry (value 0) would win."""
+    out = {}
+    x = np.abs(_rand(113, 4200, 40)) + 0.25                     # 4200 = 32 * 128 + 104: 24 padding columns
+    out["neg_q130"] = _case(x, 9, -1, q=-(np.abs(_rand(114, 130, 40)) + 0.25))
+    x = np.abs(_rand(115, 1000, 40)) + 0.25
+    x[40, 3] = 131072.0
+    out["neg_flagged"] = _case(x, 9, 300, q=-x[300:430])       # the exact pass with a self entry
+    out["simplex120"] = _case(simplex_rows(), 5, 0)             # 8 padding columns, all values tie at -1 / 128
+    return out
+
+
+def same_no_self_case():
+    """Q is X with nothing excluded: every row's first neighbour is itself, or its lowest-index duplicate."""
+    x = _rand(116, 1000, 64)
+    x[11] = x[12] = x[13] = x[10]
+    return _case(x, 5, -1)
+
+
 def vote_case():
     """(idx [300, 8], dot, labels in {-1, 0 .. 3}): uniform ties, negative labels, and row 0 with no valid neighbour."""
     x = _rand(40, 300, 8)
@@ -211,18 +299,23 @@ def f16_flushed(a):
     return h
 
 
-def ranges(m, n, k):
-    """(ny, tiles_per_y) of scd_knn on a device of 256 compute units."""
-    panels, tiles = -(-m // 128), -(-n // 128)
-    ny = min(32, tiles, max(-(-1024 // panels), -(-k // 4)))
+def ranges(m, n, k, cu=256):
+    """(ny, tiles_per_y) of scd_knn on a device of cu compute units, by the host code's two steps: ny_max (what the workspace is sized
+    for) from 1024 blocks, then ny from 4 cu."""
+    panels, tiles = -(-m // TILE), -(-n // TILE)
+    ny_max = min(32, tiles, max(-(-1024 // panels), -(-k // 4)))
+    ny = max(1, min(ny_max, max(-(-4 * cu // panels), -(-k // 4))))
     per = -(-tiles // ny)
     return -(-tiles // per), per
 
 
-def simulate_filter(case, slots):
+def simulate_filter(case, slots, cu=256, scale=1.0, with_bound=False):
     """The candidate count of every row as scd_knn's two passes form it - float32 dots of the flushed fp16 rows (numpy's summation order,
     not the MFMA's: a simulation), t_i = the k-th largest of the per-range, per-residue-class maxima, every admissible column with
-    approximate dot >= t_i - 2 B_i counts.  A row that keeps fewer than k columns has no bound: it gets 2 * slots + 1."""
+    approximate dot >= t_i - 2 B_i (rounded down to fp32, as the device rounds it) counts.  A row that keeps fewer than k columns has no
+    bound: it gets 2 * slots + 1.  On exact-grid rows (every fp16 copy exact, every dot exact in fp32 in any order) this is no simulation
+    but the device's count, as long as the float32 rounding of h_i cannot move it: `scale` multiplies B_i to show that it cannot.
+    with_bound: also the mask of the rows that have a bound."""
     q, x, k, self_base = case["q"], case["x"], case["k"], case["self_base"]
     m, n, d = q.shape[0], x.shape[0], x.shape[1]
     hq, hx = f16_flushed(q), f16_flushed(x)
@@ -233,17 +326,29 @@ def simulate_filter(case, slots):
     e_x = np.sqrt(((x.astype(np.float64) - hx) ** 2).sum(1))
     h_q, h_x = np.sqrt((hq.astype(np.float64) ** 2).sum(1)), np.sqrt((hx.astype(np.float64) ** 2).sum(1))
     dp = -(-d // 32) * 32
-    b = (e_q * (h_x.max() + e_x.max()) + h_q * e_x.max() + 2.0 ** -22 * (dp // 32 + 1) * h_q * h_x.max()) * 1.001
-    ny, per = ranges(m, n, k)
+    b = (e_q * (h_x.max() + e_x.max()) + h_q * e_x.max() + 2.0 ** -22 * (dp // 32 + 1) * h_q * h_x.max()) * 1.001 * scale
+    ny, per = ranges(m, n, k, cu)
     col = np.arange(n)
-    bins = (col // (128 * per)) * 16 + col % 16
+    bins = (col // (TILE * per)) * 16 + col % 16
     kept = np.full((m, ny * 16), -np.inf, dtype=np.float32)
     for bn in np.unique(bins):
         kept[:, bn] = s[:, bins == bn].max(1)
-    counts = np.full(m, 2 * slots + 1, dtype=np.int64)
+    counts, bounded = np.full(m, 2 * slots + 1, dtype=np.int64), np.zeros(m, dtype=bool)
     for i in range(m):
         row = kept[i][kept[i] > -np.inf]
         if len(row) >= k:
             t = np.partition(row, len(row) - k)[len(row) - k]
-            counts[i] = int((s[i] >= np.nextafter(np.float32(float(t) - 2.0 * b[i]), np.float32(-np.inf))).sum())      # rounded down, or lower
-    return counts
+            want = float(t) - 2.0 * b[i]
+            theta = np.float32(want)
+            if float(theta) > want:                             # to nearest went up: one down is the value rounded down
+                theta = np.nextafter(theta, np.float32(-np.inf))
+            counts[i], bounded[i] = int((s[i] >= theta).sum()), True
+    return (counts, bounded) if with_bound else counts
+
+
+def filter_info(case, slots, cu=256):
+    """(info[0], info[2], info[3]) of scd_knn as simulate_filter predicts them: rows through the exact pass (no bound, or more candidates
+    than slots), rows whose slots overflowed, the largest candidate count of a row (a row without a bound emits nothing)."""
+    counts, bounded = simulate_filter(case, slots, cu, with_bound=True)
+    over = bounded & (counts > slots)
+    return int((~bounded).sum() + over.sum()), int(over.sum()), int(counts[bounded].max()) if bounded.any() else 0

@@ -1,7 +1,7 @@
 """GPU checks of the FINCH primitives (scd_amd/csrc/finch.hip), scd_amd.finch and the two drivers on top of them.
 
 The kernels are checked bit for bit: first-neighbour and pair-distance inputs lie on a grid (multiples of 2^-4, or of 2^-20 for the
-near-tie ladder, |x| <= 1), so every float64 dot is exact and every correct implementation agrees with tests/finch_cases.py's oracle in
+near-tie ladder and 2^-7 for the simplex, |x| <= 1), so every float64 dot is exact and every correct implementation agrees with tests/finch_cases.py's oracle in
 nn AND d1, ties included - no row is excused.  End to end the expected values are the reference's own partitions
 (tests/golden/finch.npz, tools/gen_finch_golden.py) on cases whose margins make that a fair demand; at a size where margins are not
 controlled every level is checked against the oracle recomputed from that level's device inputs.  docs/design/finch.md has the rules."""
@@ -15,6 +15,7 @@ import pytest
 import torch
 
 import finch_cases as fc
+import knn_cases as kc
 import silhouette_cases as sc
 from oracle import synth
 
@@ -74,6 +75,8 @@ def neighbour_cases():
     x[1:65, 0] = (np.arange(64) + 1) / 128.0
     x[1:65, 1] = 2.0 ** -20
     out["ladder"] = x
+    # every pair's dot is exactly -1 / 128: one of the 8 padding columns of the tile (approximate dot 0) would win if it were admitted
+    out["simplex120"] = kc.simplex_rows()
     return out
 
 
@@ -100,6 +103,8 @@ def test_first_neighbor_bit_for_bit(ops, name):
         assert nn[0] == 1 and nn[150] == 0 and d1[0] == 1.0 and d1[150] == 1.0
     if name == "duplicates":
         assert list(nn[10:14]) == [11, 10, 10, 10] and nn[5] == 900 and nn[900] == 5
+    if name == "simplex120":
+        assert nn.max() < 120 and nn[0] == 1 and (nn[1:] == 0).all() and (d1 == 1.0 + 1.0 / 128).all()
 
 
 def test_first_neighbor_limits(ops):

@@ -127,6 +127,101 @@ def test_filter_path_decides(ops, blobs, name):
     assert case["k"] <= info[3] <= 512
 
 
+# ------------------------------------------------------------------------------------------------- the paths that need n > 4096
+# tests/test_knn_host.py asserts what each case is named for: the tiles per range on any device, the chunks, the negative maxima.
+TILES = kc.tile_cases()
+
+
+@pytest.mark.parametrize("name", list(TILES))
+def test_several_tiles_per_range(ops, name):
+    """More than 32 tiles: a range of both MFMA passes holds 2 or 3 tiles, so the running maximum is carried across tiles, the LDS ring
+    is filled again behind the last barrier, the last range is cut short, and a self column lies in the second tile of its range.  The
+    simulated filter gives every row at most 256 candidates, so the exact pass alone cannot pass these."""
+    case = TILES[name]
+    m = case["q"].shape[0]
+    idx, dot, info = check(ops, case, name)
+    assert info[1] == 0 and info[0] + info[2] <= m // 10
+    if name == "t33_q129":
+        assert idx[5][0] == 4096 and idx[77][0] == 4095         # the one valid column of the last tile, and the last of the tile before
+    if name == "border_shard":                                  # again with Q a view into x: the same bits as with a copy of those rows
+        a, b = kc.BORDER
+        x = dev(case["x"])
+        v_idx, v_dot, v_info = ops.knn(x[a:b], x, case["k"], a)
+        assert x[a:b].data_ptr() == x.data_ptr() + a * x.shape[1] * 4
+        assert np.array_equal(v_idx.cpu().numpy(), idx) and np.array_equal(v_dot.cpu().numpy(), dot)
+        assert np.array_equal(v_info.cpu().numpy(), info)
+        assert not (idx == (a + np.arange(b - a))[:, None]).any()
+
+
+CHUNKED = kc.chunk_cases()
+
+
+@pytest.mark.parametrize("name", list(CHUNKED))
+def test_exact_pass_many_chunks(ops, name):
+    """The exact pass over 2 to 10 chunks of 448 columns with distinct values: columns of later chunks displace earlier ones, 64 best
+    so far + 448 fill the LDS arrays exactly, a last chunk of one column, the self entry in a later chunk."""
+    case = CHUNKED[name]
+    m = case["q"].shape[0]
+    _, _, info = check(ops, case, name)
+    if name in ("hub", "offset"):                               # every row has a bound, and more candidates than slots
+        assert info[1] == 0 and info[0] == m and info[2] == m and info[3] > 512
+    else:                                                       # a value that does not fit fp16: no row has a bound
+        assert info[1] == 1 and info[0] == m and info[2] == 0
+
+
+NEGATIVE = kc.negative_cases()
+
+
+@pytest.mark.parametrize("name", list(NEGATIVE))
+def test_negative_dots(ops, name):
+    """Every admissible dot is negative, so a padding column (approximate dot 0) or the exact pass's self entry (value 0) would win."""
+    case = NEGATIVE[name]
+    n = case["x"].shape[0]
+    idx, dot, info = run(ops, case)
+    print("knn %-24s exact rows %d, flag %d, overflowed rows %d, most candidates %d" % (name, info[0], info[1], info[2], info[3]))
+    assert idx.max() < n and idx.min() >= 0, "a padding column or an empty entry leaked into the answer"
+    want_idx, want_dot = kc.knn_f64(case["q"], case["x"], case["k"], case["self_base"])
+    assert np.array_equal(idx, want_idx)
+    assert np.array_equal(dot, want_dot)                        # float64, bit for bit
+    assert dot.max() < 0
+    if name == "neg_flagged":
+        assert info[1] == 1 and info[0] == case["q"].shape[0]
+        assert not (idx == (case["self_base"] + np.arange(idx.shape[0]))[:, None]).any()
+    else:
+        assert info[1] == 0 and info[0] == 0                    # the filter decided these
+    if name == "simplex120":
+        assert list(idx[0]) == [1, 2, 3, 4, 5] and list(idx[3]) == [0, 1, 2, 4, 5] and list(idx[119]) == [0, 1, 2, 3, 4]
+
+
+def test_same_buffer_without_exclusion(ops):
+    """One device buffer as Q and as X with self_base = -1: one preparation serves both sides and nothing is excluded."""
+    case = kc.same_no_self_case()
+    x = dev(case["x"])
+    idx, dot, info = ops.knn(x, x, case["k"], -1)
+    idx, dot = idx.cpu().numpy(), dot.cpu().numpy()
+    want_idx, want_dot = kc.knn_f64(case["q"], case["x"], case["k"], -1)
+    assert np.array_equal(idx, want_idx) and np.array_equal(dot, want_dot)
+    first = np.arange(1000)
+    first[11:14] = 10                                           # the lowest-index duplicate
+    assert np.array_equal(idx[:, 0], first) and list(idx[12][:4]) == [10, 11, 12, 13]
+    c_idx, c_dot, _ = ops.knn(x.clone(), x, case["k"], -1)      # two buffers: two preparations, the same bits
+    assert np.array_equal(c_idx.cpu().numpy(), idx) and np.array_equal(c_dot.cpu().numpy(), dot)
+
+
+@pytest.mark.parametrize("name", ["border_shard", "ties", "simplex120"])
+def test_filter_counts_equal_the_model(ops, name):
+    """Exact-grid rows: e_i = 0 and every approximate dot is exact in fp32 in any order, so knn_cases.simulate_filter is no simulation
+    but the device's own count (tests/test_knn_host.py: no count moves when B_i is scaled by 1 +- 2^-10).  A bound too loose, or a
+    threshold from another rank, still returns the right neighbours - and shows here."""
+    case = {"border_shard": TILES["border_shard"], "ties": kc.tie_case(), "simplex120": NEGATIVE["simplex120"]}[name]
+    cu = torch.cuda.get_device_properties(0).multi_processor_count
+    want = kc.filter_info(case, ops._L().scd_knn_slots(), cu)
+    _, _, info = run(ops, case)
+    print("knn %-24s on %d compute units: info %s, the model (exact rows, overflowed rows, most candidates) %s" % (name, cu, [int(v) for v in info], want))
+    assert info[1] == 0
+    assert (info[0], info[2], info[3]) == want
+
+
 # ------------------------------------------------------------------------------------------------- the vote
 @pytest.mark.parametrize("mode", ["uniform", "softmax"])
 def test_vote_against_restatement(ops, mode):
