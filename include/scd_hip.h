@@ -456,6 +456,30 @@ int scd_knn(scd_handle h, const float* Q, int64_t m, const float* X, int64_t n, 
 int scd_knn_vote(scd_handle h, const int32_t* idx, const double* dot, int64_t m, int k_stride, int k_use, const int32_t* base_labels,
                  int64_t n, int mode, double temperature, int32_t* pred_out, double* score_out, void* stream);
 
+/* ---- HDBSCAN on unit rows (no counterpart in the reference; scikit-learn 1.7.2's sklearn.cluster.HDBSCAN(metric='euclidean',
+ *      algorithm='brute'); docs/design/hdbscan.md) ---- */
+/* One Boruvka round of the minimum spanning tree of the mutual-reachability graph, without the n x n matrix that
+ * sklearn/cluster/_hdbscan/_reachability.pyx (mutual_reachability_graph) and hdbscan.py:_brute_mst build.  U float32 [n, d], core double
+ * [n] (the core dot of each row: the float64 dot with its (min_samples - 1)-th nearest other row, or +inf), comp int32 [n] (any values:
+ * the component of each row).  With v_ij the float64 dot of rows i and j (scd_knn's) and r_ij = min(core_i, core_j, v_ij):
+ * nn_out[i] = the column j with comp[j] != comp[i] of the largest r_ij, ties to the lowest j; r_out[i] = that r_ij (double); a row without
+ * a foreign column gets -1 and -inf.  info_out int32 [4] as scd_knn's.  Two fp16 MFMA passes with an error bound computed from the rows
+ * propose candidates, float64 decides; the result never depends on them; two calls return the same bits.
+ * prepared: 0 makes the fp16 copy of U and its row statistics in the workspace; 1 says the workspace still holds them from an earlier
+ * call with this U, n and d (the rounds of one fit).  Limits: 2 <= n < 2^31, d rounded up to 32 <= 1024; scd_mr_nearest_ws_bytes returns 0
+ * outside them.  The workspace holds the fp16 copy of U and scd_knn_slots() int32 slots per row: 0.47 GB at n = 126,976, d = 768. */
+size_t scd_mr_nearest_ws_bytes(int64_t n, int d);
+int scd_mr_nearest(scd_handle h, const float* U, int64_t n, int d, const double* core, const int32_t* comp, int prepared, int32_t* nn_out,
+                   double* r_out, int32_t* info_out, void* ws, size_t ws_bytes, void* stream);
+/* HOST.  _linkage.pyx:make_single_linkage and _tree.pyx:tree_to_labels (_condense_tree, _compute_stability, _get_clusters, _do_labelling,
+ * get_probabilities; cluster_selection_epsilon = 0, max_cluster_size = None) on the n - 1 edges (lo[e], hi[e], weight[e]) of a spanning
+ * tree in the order given (sorted by weight ascending; edge e joins as current_node = lo, next_node = hi): lambda = 1 / weight, +inf at
+ * weight 0.  method 0 = 'eom', 1 = 'leaf'.  labels_out int32 [n] (noise = -1, clusters numbered as scikit-learn numbers them), prob_out
+ * double [n], n_clusters_out int32 [1].  SCD_EINVAL: n < 2, min_cluster_size < 2, an index outside [0, n), edges that form no spanning
+ * tree, a NaN weight.  No recursion: a path-shaped tree costs no stack. */
+int scd_hdbscan_tree(const int32_t* lo, const int32_t* hi, const double* weight, int64_t n, int min_cluster_size, int method,
+                     int allow_single_cluster, int32_t* labels_out, double* prob_out, int32_t* n_clusters_out);
+
 /* ---- the linear probe: multinomial logistic regression on frozen features (the linear evaluation of DINO / DINOv2; scikit-learn's
  *      LogisticRegression(C) written as a sum; the reference trains the same head in gcd/methods/cluster_and_classifier/
  *      train_supervised.py; docs/design/probe.md) ---- */

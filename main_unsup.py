@@ -8,6 +8,8 @@ Here every stage starts from the reference's own cache files under --root_dir, b
   extracted_features/clip_{dataset}_all.pt           same dict, CLIP features                          (:306-311)
   cluster/{cluster}_{feat_model}_{dataset}_{n_cluster}.pt   dict all_preds, u_preds, u_targets, mask  (:366-374)
                                                             ({cluster} = KM, SSKM, ConSSKM, FINCH or SC)
+  cluster/HDBSCAN_{feat_model}_{dataset}_mcs{min_cluster_size}[_ms{min_samples}].pt   the same dict plus noise, probabilities, n_cluster
+                                                            (--cluster HDBSCAN: the number of clusters is a result, not a flag)
   zeroshot_weights/zeroshot_weights_all_{nouns|wikibird|wikidog}_vit_b_16.pt   tensor [512, V]        (:389-394)
 --clip_model picks the CLIP backbone (clip.available_models(), default ViT-B/16: the names above).  With another one every
 CLIP-derived cache carries its tag, so that no cache of one backbone is read as another's features:
@@ -62,11 +64,15 @@ def build_parser():
     p.add_argument('--extract_feat', type=str2bool, default=False)
     p.add_argument('--run_cluster', type=str2bool, default=False)
     p.add_argument('--cluster', type=str, default='KM', help='options: KM, SSKM, ConSSKM, FINCH (first-neighbour clustering refined to --n_cluster clusters), '
-                                                                     'SC (spectral clustering on the exact k-NN graph, see --n_neighbors)')
+                                                                     'SC (spectral clustering on the exact k-NN graph, see --n_neighbors), '
+                                                                     'HDBSCAN (no --n_cluster: the number of clusters is a result, see --min_cluster_size)')
     p.add_argument('--save_cluster', type=str2bool, default=False)
     p.add_argument('--n_cluster', type=int, default=1000)
     p.add_argument('--n_neighbors', type=int, default=10,
                    help="--cluster SC: neighbours per row of the graph, the row itself included (scikit-learn's n_neighbors), 2 to 65")
+    p.add_argument('--min_cluster_size', type=int, default=5, help="--cluster HDBSCAN: scikit-learn's min_cluster_size")
+    p.add_argument('--min_samples', type=int, default=None,
+                   help="--cluster HDBSCAN: scikit-learn's min_samples, the row itself included, 1 to 65 (default: min_cluster_size)")
     p.add_argument('--cluster_size_min', type=int, default=50)
     p.add_argument('--cluster_size_max', type=int, default=1200)
     p.add_argument('--corpus', type=str, default='wordnet', help='options: wordnet, wikibird, wikidog')
@@ -115,6 +121,25 @@ def run_clustering(args, u_feats, l_feats, l_targets):
     km.fit_mix(u.float(), l.float(), lt)
     all_preds = km.labels_.cpu().numpy()
     return all_preds, all_preds[len(l_targets):]
+
+
+def run_hdbscan(args, u_feats):
+    """--cluster HDBSCAN on the unlabelled rows (docs/design/hdbscan.md).  The naming stage needs a full partition, so each noise row
+    joins the cluster of its nearest clustered row.  Returns the extra entries of the result file: u_preds (the full partition), noise
+    (bool per unlabelled row), probabilities, n_cluster (a RESULT of the fit)."""
+    from scd_amd.hdbscan import HDBSCAN, attach_noise
+    x = np.asarray(u_feats, dtype=np.float32)
+    h = HDBSCAN(min_cluster_size=args.min_cluster_size, min_samples=args.min_samples).fit(x)
+    print(f"HDBSCAN: {h.n_clusters_} clusters, {int((h.labels_ < 0).sum())} noise rows of {len(x)}, {h.info_['rounds']} rounds")
+    return dict(u_preds=attach_noise(x, h.labels_), noise=h.labels_ < 0, probabilities=h.probabilities_, n_cluster=int(h.n_clusters_))
+
+
+def cluster_result_name(args):
+    """{cluster}_{feat_model}_{dataset}_{n_cluster}.pt; HDBSCAN's result is named by its parameters, the cluster count being a result."""
+    tag = str(args.n_cluster)
+    if args.cluster == 'HDBSCAN':
+        tag = f'mcs{args.min_cluster_size}' + ('' if args.min_samples is None else f'_ms{args.min_samples}')
+    return f'{args.cluster}_{feat_cache_name(args)}_{args.dataset_name}_{tag}.pt'
 
 
 def load_or_extract(args, model, feat_model_name, out_name):
@@ -260,17 +285,25 @@ def main(argv=None):
     mask = np.asarray(mask_cls, dtype=bool)[~mask_lab]
 
     cdir = os.path.join(args.root_dir, 'cluster')
-    cpath = os.path.join(cdir, f'{args.cluster}_{feat_cache_name(args)}_{args.dataset_name}_{args.n_cluster}.pt')
+    cpath = os.path.join(cdir, cluster_result_name(args))
     if args.run_cluster or args.synthetic:
         print(f'Fitting {args.cluster} ...')
-        all_preds, preds = run_clustering(args, u_feats, l_feats, l_targets)
-        cluster_result = dict(all_preds=all_preds, u_preds=preds, u_targets=u_targets, mask=mask)
+        if args.cluster == 'HDBSCAN':
+            cluster_result = dict(all_preds=None, u_targets=u_targets, mask=mask, **run_hdbscan(args, u_feats))
+        else:
+            all_preds, preds = run_clustering(args, u_feats, l_feats, l_targets)
+            cluster_result = dict(all_preds=all_preds, u_preds=preds, u_targets=u_targets, mask=mask)
         if args.save_cluster:
             os.makedirs(cdir, exist_ok=True)
             torch.save(cluster_result, cpath)
     else:
         cluster_result = torch.load(cpath, weights_only=False)
     preds = cluster_result['u_preds']
+    if args.cluster == 'HDBSCAN':                               # the number of clusters is a result: the naming stage takes it from here
+        args.n_cluster = int(cluster_result['n_cluster'])
+        print(f"HDBSCAN: n_cluster = {args.n_cluster}")
+        if args.n_cluster == 0:
+            raise SystemExit("HDBSCAN found no cluster (every row is noise): nothing to name; try a smaller --min_cluster_size")
     all_acc, old_acc, new_acc = split_cluster_acc_v2(y_true=u_targets, y_pred=preds, mask=mask)
     print(f"{args.cluster} Accuracies: All {all_acc} | Old {old_acc} | New {new_acc}")
 

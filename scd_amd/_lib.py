@@ -167,6 +167,11 @@ SIGNATURES = {
     "scd_knn_affinity": (_i, [_vp, _vp, _i64, _i, _vp, _vp, _vp, _vp, _i64, C.POINTER(_i64), _vp, _sz, _vp]),
     # h, rowptr, col, val, n, X, ldx, m, alpha, beta, gamma, Z, ldz, Y, ldy, stream
     "scd_spmm_f64": (_i, [_vp, _vp, _vp, _vp, _i64, _vp, _i64, _i, C.c_double, C.c_double, C.c_double, _vp, _i64, _vp, _i64, _vp]),
+    "scd_mr_nearest_ws_bytes": (_sz, [_i64, _i]),
+    # h, U, n, d, core, comp, prepared, nn_out, r_out, info_out, ws, ws_bytes, stream
+    "scd_mr_nearest": (_i, [_vp, _vp, _i64, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    # lo, hi, weight, n, min_cluster_size, method, allow_single_cluster, labels_out, prob_out, n_clusters_out
+    "scd_hdbscan_tree": (_i, [_vp, _vp, _vp, _i64, _i, _i, _i, _vp, _vp, C.POINTER(C.c_int32)]),
     "scd_munkres": (_i, [_vp, _i, _i, _vp, C.POINTER(_i)]),
     "scd_munkres_sparse": (_i, [_i, _i64, _vp, _vp, _vp, _vp, C.POINTER(_i)]),
     "scd_transport_solve": (_i, [_vp, _i64, _i, _i, _i, _vp, C.POINTER(_i64)]),

@@ -997,6 +997,64 @@ def knn_vote(idx, dot, base_labels, k_use=None, mode=KNN_SOFTMAX, temperature=0.
     return pred, score
 
 
+# ----------------------------------------------------------------------------- HDBSCAN primitives (docs/design/hdbscan.md)
+def mr_nearest_workspace(u):
+    """The workspace of `mr_nearest` for u float32 [n, d]: allocate once per fit and pass it to every round, so that the fp16 copy of u is
+    made once (the first call with prepared=False)."""
+    _need_cuda(u)
+    if u.dim() != 2 or u.dtype != torch.float32:
+        raise _lib.ScdError(_lib.SCD_EINVAL, "mr_nearest: u must be float32 [n, d]")
+    nb = _L().scd_mr_nearest_ws_bytes(u.shape[0], u.shape[1])
+    if nb == 0:
+        raise _lib.ScdError(_lib.SCD_EINVAL, "mr_nearest: n = %d, d = %d outside the limits 2 <= n < 2^31, d <= 1024" % tuple(u.shape))
+    return _ws(nb, u.device)
+
+
+def mr_nearest(u, core, comp, ws=None, prepared=False):
+    """scd_mr_nearest, one Boruvka round: u float32 [n, d], core float64 [n] (core dots, +inf allowed), comp int32 [n] on the device ->
+    (nn int32 [n], r float64 [n], info int32 [4]).  nn[i] = the column j with comp[j] != comp[i] of the largest min(core_i, core_j,
+    float64 dot of rows i and j), ties to the lowest j; r[i] = that value; -1 and -inf for a row without a foreign column.
+    ws: `mr_nearest_workspace(u)`; prepared=True says it still holds this u's fp16 copy from an earlier call."""
+    _need_cuda(u, core, comp)
+    if u.dim() != 2 or u.dtype != torch.float32 or core.dtype != torch.float64 or comp.dtype != torch.int32 \
+            or core.shape != (u.shape[0],) or comp.shape != (u.shape[0],):
+        raise _lib.ScdError(_lib.SCD_EINVAL, "mr_nearest: u float32 [n, d], core float64 [n], comp int32 [n]")
+    if not u.is_contiguous():
+        raise _lib.ScdError(_lib.SCD_EINVAL, "mr_nearest: u must be contiguous (the workspace's copy belongs to this tensor)")
+    core, comp = core.contiguous(), comp.contiguous()
+    n, d = u.shape
+    if ws is None:
+        ws, prepared = mr_nearest_workspace(u), False
+    nn = torch.empty(n, dtype=torch.int32, device=u.device)
+    r = torch.empty(n, dtype=torch.float64, device=u.device)
+    info = torch.empty(4, dtype=torch.int32, device=u.device)
+    check(_L().scd_mr_nearest(handle(), ptr(u), n, d, ptr(core), ptr(comp), 1 if prepared else 0, ptr(nn), ptr(r), ptr(info), ptr(ws),
+                              ws.numel(), stream_ptr()))
+    return nn, r, info
+
+
+HDBSCAN_METHODS = {"eom": 0, "leaf": 1}
+
+
+def hdbscan_tree(lo, hi, weight, min_cluster_size, method="eom", allow_single_cluster=False):
+    """scd_hdbscan_tree (host): the n - 1 sorted edges (lo, hi, weight) of a spanning tree -> (labels int64 [n] with noise = -1,
+    probabilities float64 [n], the number of clusters): scikit-learn's make_single_linkage + tree_to_labels."""
+    lo = np.ascontiguousarray(lo, dtype=np.int32)
+    hi = np.ascontiguousarray(hi, dtype=np.int32)
+    w = np.ascontiguousarray(weight, dtype=np.float64)
+    if method not in HDBSCAN_METHODS:
+        raise _lib.ScdError(_lib.SCD_EINVAL, "hdbscan_tree: cluster_selection_method %r is not one of %s" % (method, sorted(HDBSCAN_METHODS)))
+    if not (lo.ndim == hi.ndim == w.ndim == 1 and lo.size == hi.size == w.size):
+        raise _lib.ScdError(_lib.SCD_EINVAL, "hdbscan_tree: lo, hi and weight must be vectors of one length")
+    n = lo.size + 1
+    labels = np.empty(n, dtype=np.int32)
+    prob = np.empty(n, dtype=np.float64)
+    nclu = C.c_int32(0)
+    check(_L().scd_hdbscan_tree(ptr(lo), ptr(hi), ptr(w), n, int(min_cluster_size), HDBSCAN_METHODS[method], 1 if allow_single_cluster else 0,
+                                ptr(labels), ptr(prob), C.byref(nclu)))
+    return labels.astype(np.int64), prob, int(nclu.value)
+
+
 # ----------------------------------------------------------------------------- the linear probe (docs/design/probe.md)
 def _probe_args(who, x, w, b):
     _need_cuda(x, w)
