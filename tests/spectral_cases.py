@@ -1,6 +1,7 @@
 """The float64 restatement of spectral clustering on the k-NN graph (docs/design/spectral.md) and the cases of its tests: the affinity
 from exact float64 k-NN lists (knn_cases.knn_f64), S = D^-1/2 A D^-1/2, scd_spmm_f64's chunked summation order in numpy, and the
-embedding from a dense numpy.linalg.eigh.  Nothing here uses a device or scd_amd."""
+embedding from a dense numpy.linalg.eigh; affinity_sparse restates the affinity without n x n arrays for the cases of more than one
+tile of graph_scan_kernel (SCAN).  Nothing here uses a device or scd_amd."""
 import numpy as np
 
 import knn_cases as kc
@@ -35,6 +36,36 @@ def affinity(idx, n=None):
     rowptr = np.zeros(n + 1, dtype=np.int64)
     np.cumsum(np.bincount(rows, minlength=n), out=rowptr[1:])
     return dict(rowptr=rowptr, col=cols.astype(np.int32), val=val, inv_sqrt_deg=1.0 / root, nnz=len(cols), deg=deg, A=a)
+
+
+def affinity_sparse(idx, n=None):
+    """affinity() without the n x n arrays, for lists of many rows: the same dict without `A`, every field with the same bits."""
+    idx = np.asarray(idx).astype(np.int64)
+    n = idx.shape[0] if n is None else n
+    rows = np.repeat(np.arange(idx.shape[0], dtype=np.int64), idx.shape[1])
+    t = idx.reshape(-1)
+    keep = (t >= 0) & (t != rows)
+    if (t[keep] >= n).any():
+        raise ValueError("index >= n")
+    fwd = np.unique(rows[keep] * n + t[keep])                   # the entries of C: a repeated neighbour counts once
+    back = (fwd % n) * n + fwd // n
+    keys = np.union1d(fwd, back)                                # row-major: columns ascend inside a row
+    r, c = keys // n, keys % n
+    a = np.where(np.isin(keys, fwd) & np.isin(c * n + r, fwd), 1.0, 0.5)
+    deg = np.bincount(r, weights=a, minlength=n)                # multiples of 0.5 below 2^52: exact in any order
+    root = np.where(deg > 0, np.sqrt(deg), 1.0)
+    rowptr = np.zeros(n + 1, dtype=np.int64)
+    np.cumsum(np.bincount(r, minlength=n), out=rowptr[1:])
+    return dict(rowptr=rowptr, col=c.astype(np.int32), val=a / (root[r] * root[c]), inv_sqrt_deg=1.0 / root, nnz=len(keys), deg=deg)
+
+
+SCAN_TILE = 4096                # graph_scan_kernel: rows per tile of the prefix sum, GRAPH_SCAN_THREADS * GRAPH_SCAN_PER
+
+
+def carry_zero(rowptr):
+    """The planted mistake of the scan: every tile of SCAN_TILE rows starts from 0 instead of the rows before it."""
+    i = np.arange(len(rowptr))
+    return rowptr - rowptr[(i // SCAN_TILE) * SCAN_TILE]
 
 
 def dense_s(aff):
@@ -177,6 +208,29 @@ def ragged():
     idx[1::7, 4] = idx[1::7, 1]                                 # a neighbour (or a -1) twice
     idx[3::11, 0] = idx[3::11, 6]
     return idx.astype(np.int32)
+
+
+def scan_lists(n, k, seed):
+    """Lists for more than one tile of the row-length scan, in ragged()'s style (-1 entries, a self index, a repeated neighbour), with a
+    hub at the first row of the second tile - row 4,096 is in the list of every 4th row, so its own row is longer than one wave ranks
+    alone (1,024) and than two chunks of the product - and, just before it, row 4,095 with an empty list that nobody points to."""
+    rs = np.random.RandomState(seed)
+    idx = rs.randint(0, n, size=(n, k))
+    idx[rs.rand(n, k) < 0.15] = -1
+    idx[::5, 2] = np.arange(n)[::5]                             # the row itself
+    idx[1::7, 1] = idx[1::7, 0]                                 # a neighbour (or a -1) twice
+    idx[::4, 0] = SCAN_TILE
+    idx[idx == SCAN_TILE - 1] = -1
+    idx[SCAN_TILE - 1] = -1
+    return idx.astype(np.int32)
+
+
+SCAN = {"scan_4097": (4097, 3, 3), "scan_8200": (8200, 5, 4)}   # name -> (n, k, seed): a second tile of ONE row; three tiles
+
+
+def scan_cases():
+    """name -> idx int32 [n, k]: too many rows for affinity()'s dense arrays; affinity_sparse is their restatement."""
+    return {name: scan_lists(*args) for name, args in SCAN.items()}
 
 
 def list_cases():

@@ -22,12 +22,12 @@ def ops():
 
 @pytest.fixture(scope="module")
 def lists():
-    return sc.list_cases()
+    return dict(sc.list_cases(), **sc.scan_cases())
 
 
 @pytest.fixture(scope="module")
 def affs(lists):
-    return {name: sc.affinity(idx) for name, idx in lists.items()}
+    return {name: (sc.affinity_sparse if name in sc.SCAN else sc.affinity)(idx) for name, idx in lists.items()}
 
 
 @pytest.fixture(scope="module")
@@ -55,12 +55,14 @@ def assert_affinity(got, want):
 
 
 # ------------------------------------------------------------------------------------------------- the affinity
-@pytest.mark.parametrize("name", ["blobs", "rings", "hub", "tiny", "ragged", "hub_wide"])
+@pytest.mark.parametrize("name", ["blobs", "rings", "hub", "tiny", "ragged", "hub_wide", "scan_4097", "scan_8200"])
 def test_affinity_bit_for_bit(ops, lists, affs, name):
     idx = dev(lists[name])
     first = ops.knn_affinity(idx)
     lens = np.diff(affs[name]["rowptr"])
     print("affinity %-6s n %4d k %2d: nnz %5d, median row %d, longest row %d" % (name, idx.shape[0], idx.shape[1], first[4], np.median(lens), lens.max()))
+    if name in sc.SCAN:                                         # graph_scan_kernel hands a carry from tile to tile
+        assert affs[name]["rowptr"][sc.SCAN_TILE] > 0 and lens[sc.SCAN_TILE] > 1024
     assert_affinity(first, affs[name])
     second = ops.knn_affinity(idx, cap=2 * idx.numel() + 100)
     for a, b in zip(first[:4], second[:4]):
@@ -102,8 +104,8 @@ def upload(aff):
 
 
 @pytest.mark.parametrize("coeffs", list(COEFFS))
-@pytest.mark.parametrize("m", [8, 40, 136])
-@pytest.mark.parametrize("name", ["blobs", "hub", "ragged", "hub_wide"])
+@pytest.mark.parametrize("name,m", [(name, m) for m in (8, 40, 136) for name in ("blobs", "hub", "ragged", "hub_wide")]
+                         + [(name, m) for m in (8, 136) for name in sc.SCAN])
 def test_spmm_bit_for_bit(ops, affs, name, m, coeffs):
     aff = affs[name]
     n = len(aff["rowptr"]) - 1

@@ -150,13 +150,105 @@ def test_gradient_against_restatement(ops, n):
         assert abs(float(kle.item()) - (klp + np.log(Z) * psum)) <= 1e-12 * (abs(klp) + abs(np.log(Z) * psum))
 
 
-def test_gradient_two_calls_same_bits(ops):
-    Y, P = reference(3001, "converged")[:2]
+TORCH_RTOL = 1e-13              # tests/test_tsne_host.py: repulsion_f64_torch against repulsion_f64
+
+
+def large_reference(name, state):
+    """As reference() for a case of tc.LARGE: the float64 sums are tsne_cases.repulsion_f64_torch on the device (plain torch float64
+    operations, no code of scd_amd), P is banded_p; computed once per case."""
+    n = tc.LARGE[name]
+    if (n, state) not in _REF:
+        Y = tc.state(state, n)
+        if n not in _P:
+            _P[n] = tc.banded_p(n, seed=11)
+        P = _P[n]
+        _REF[(n, state)] = (Y, P) + tc.repulsion_f64_torch(Y, device="cuda") + tc.attraction_f64(Y, P)
+    return _REF[(n, state)]
+
+
+def assert_hub_row(g, Fd, Zd, a, A, MA, P, what):
+    """Row 0 of banded_p alone: its attraction, taken out of the gradient with the device's own all-pairs sums, against attraction_f64."""
+    entries = int(P[0][1] - P[0][0])
+    got = g[0] / 4.0 + Fd[0] / Zd
+    err = np.abs(got - a * A[0])
+    tol = 1e-12 * (a * MA[0] + np.abs(Fd[0]) / Zd)
+    share = float(np.max(err[tol > 0] / tol[tol > 0])) if (tol > 0).any() else 0.0
+    print("%s: hub row 0 has %d entries (%d trips of the lane loop), attraction error %.3g of its bound" % (what, entries, -(-entries // 64), share))
+    assert entries > 192 and (err <= tol).all()
+
+
+@pytest.mark.parametrize("name", list(tc.LARGE))
+def test_gradient_ranges_of_several_chunks(ops, name):
+    """More than 32 chunks: every block of tsne_repulse_kernel walks a range of several chunks (the second trip of the chunk loop, `check`
+    changing between the chunks of a block, the clamp of the last range, the range count after the 'no empty range' step, a last chunk
+    of ONE column).  The same bound as test_gradient_against_restatement: its derivation does not depend on n."""
+    n = tc.LARGE[name]
+    n_cu = torch.cuda.get_device_properties(0).multi_processor_count
+    triple = tc.ranges(n, n_cu)
+    print("gradient %s: n = %d on %d compute units: %d ranges of %d chunks, %d in the last" % ((name, n, n_cu) + triple))
+    assert triple[1] >= 2
+    rows = tc.range_rows(n)
+    for state in tc.LARGE_STATES[name]:
+        Y, P, F, z, MF, A, klp, psum, MA = large_reference(name, state)
+        # the reference itself, on the rows of the host test's sensitivity check, against the numpy restatement
+        Fn, zn, MFn = tc.repulsion_f64(Y, rows=rows)
+        assert (np.abs(F[rows] - Fn) <= TORCH_RTOL * MFn).all() and (np.abs(MF[rows] - MFn) <= TORCH_RTOL * MFn).all()
+        assert (np.abs(z[rows] - zn) <= TORCH_RTOL * zn).all()
+        a = 12.0 if state == "initial" else 1.0
+        y, (indptr, indices, values) = dev(Y), dev_csr(P)
+        g0, z0, kl0, info0 = ops.tsne_gradient(y, torch.zeros(n + 1, dtype=torch.int64, device="cuda"), indices[:0], values[:0], 1.0)
+        Zd = float(z0.item())
+        Fd = -g0.cpu().numpy() * Zd / 4.0
+        Z = float(z.sum())
+        eF, eZ = np.abs(Fd - F), abs(Zd - Z)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            used = np.nanmax(np.where(MF > 0, eF / (U * MF), 0.0))
+        print("gradient %s %-10s: force error at most %.2f x 2^-24 M_i, Z error %.2f x 2^-24 Z (bound %d)" % (name, state, used, eZ / (U * Z), tc.C_BOUND))
+        assert (eF <= tc.C_BOUND * U * MF).all() and eZ <= tc.C_BOUND * U * Z
+        assert info0.cpu().tolist() == [0, 0] and float(kl0.item()) == 0.0
+        if state == "coincident":                               # exact: a skipped or repeated chunk shows as a whole number
+            assert Zd == n * (n - 1) and not Fd.any()
+        g, z1, kl, info = ops.tsne_gradient(y, indptr, indices, values, a)
+        assert float(z1.item()) == Zd and info.cpu().tolist() == [0, 0]
+        g = g.cpu().numpy()
+        want = 4.0 * (a * A - Fd / Zd)
+        tol = 1e-12 * 4.0 * (a * MA + np.abs(Fd) / Zd)
+        assert (np.abs(g - want) <= tol).all()
+        assert_hub_row(g, Fd, Zd, a, A, MA, P, "%s %s" % (name, state))
+        want_kl = klp + np.log(Zd) * psum
+        assert abs(float(kl.item()) - want_kl) <= 1e-12 * (abs(klp) + abs(np.log(Zd) * psum))
+        ge, ze, kle, _ = ops.tsne_gradient(y, indptr, indices, values, a, exact_pairs=True)
+        assert abs(float(ze.item()) - Z) <= 1e-12 * Z
+        assert (np.abs(ge.cpu().numpy() - 4.0 * (a * A - F / Z)) <= 1e-11 * 4.0 * (a * MA + MF / Z)).all()
+        assert abs(float(kle.item()) - (klp + np.log(Z) * psum)) <= 1e-12 * (abs(klp) + abs(np.log(Z) * psum))
+        if state == "coincident":
+            assert float(ze.item()) == n * (n - 1)
+
+
+def test_hub_row_attraction(ops):
+    """The attract kernel's lane loop (e += 64) on a row of more than 192 entries, at the largest size of the numpy reference."""
+    n = 3001
+    Y, P = tc.state("converged", n), tc.banded_p(n, seed=11)
+    A, klp, psum, MA = tc.attraction_f64(Y, P)
     y, (indptr, indices, values) = dev(Y), dev_csr(P)
-    first = ops.tsne_gradient(y, indptr, indices, values, 12.0)
-    second = ops.tsne_gradient(y, indptr, indices, values, 12.0)
-    for u, v in zip(first, second):
-        assert torch.equal(u, v)
+    assert (MA[0] > 0).all()
+    for a in (1.0, 12.0):
+        g0, z0, _, _ = ops.tsne_gradient(y, torch.zeros(n + 1, dtype=torch.int64, device="cuda"), indices[:0], values[:0], 1.0)
+        g, z1, kl, info = ops.tsne_gradient(y, indptr, indices, values, a)
+        Zd = float(z0.item())
+        Fd = -g0.cpu().numpy() * Zd / 4.0
+        assert float(z1.item()) == Zd and info.cpu().tolist() == [0, 0]
+        assert_hub_row(g.cpu().numpy(), Fd, Zd, a, A, MA, P, "n = %d, exaggeration %g" % (n, a))
+        assert abs(float(kl.item()) - (klp + np.log(Zd) * psum)) <= 1e-12 * (abs(klp) + abs(np.log(Zd) * psum))
+
+
+def test_gradient_two_calls_same_bits(ops):
+    for Y, P in (reference(3001, "converged")[:2], large_reference("c33", "converged")[:2]):
+        y, (indptr, indices, values) = dev(Y), dev_csr(P)
+        first = ops.tsne_gradient(y, indptr, indices, values, 12.0)
+        second = ops.tsne_gradient(y, indptr, indices, values, 12.0)
+        for u, v in zip(first, second):
+            assert torch.equal(u, v)
 
 
 # ------------------------------------------------------------------------------------------------- 8. the update step

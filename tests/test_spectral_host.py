@@ -163,6 +163,52 @@ def test_list_cases_have_what_they_are_for():
         sc.affinity(np.array([[1], [2]]))
 
 
+def bits(a):
+    return np.ascontiguousarray(a, dtype=np.float64).view(np.int64)
+
+
+def test_sparse_affinity_equals_the_dense_restatement():
+    """Field by field, the values as bits, on the six cases the dense restatement can hold."""
+    cases = sc.list_cases()
+    assert len(cases) == 6
+    for name, idx in cases.items():
+        want, got = sc.affinity(idx), sc.affinity_sparse(idx)
+        assert set(got) == set(want) - {"A"} and got["nnz"] == want["nnz"], name
+        assert np.array_equal(got["rowptr"], want["rowptr"]) and got["rowptr"].dtype == want["rowptr"].dtype, name
+        assert np.array_equal(got["col"], want["col"]) and got["col"].dtype == want["col"].dtype, name
+        for key in ("val", "inv_sqrt_deg", "deg"):
+            assert np.array_equal(bits(got[key]), bits(want[key])), (name, key)
+    with pytest.raises(ValueError):
+        sc.affinity_sparse(np.array([[1], [2]]))
+
+
+def test_scan_cases_carry():
+    """The two cases of more than 4,096 rows: a carry that is not zero, an empty row before the tile border, a hub right after it - and
+    a scan whose tiles each start from 0 gives another rowptr."""
+    cases = sc.scan_cases()
+    assert [len(cases[name]) for name in ("scan_4097", "scan_8200")] == [4097, 8200]
+    assert [sc.SCAN[name][1] for name in ("scan_4097", "scan_8200")] == [3, 5]
+    assert [-(-len(idx) // sc.SCAN_TILE) for idx in cases.values()] == [2, 3]
+    for name, idx in cases.items():
+        n = len(idx)
+        aff = sc.affinity_sparse(idx)
+        rowptr, lens = aff["rowptr"], np.diff(aff["rowptr"])
+        print("%s: nnz %d, rowptr[4096] %d, row 4096 has %d entries, median row %d" % (name, aff["nnz"], rowptr[4096], lens[4096], np.median(lens)))
+        assert rowptr[4096] > 0 and lens[4095] == 0 and aff["deg"][4095] == 0 and aff["inv_sqrt_deg"][4095] == 1.0
+        assert not (aff["col"] == 4095).any() and lens[4096] > 1024 and lens[4096] == lens.max()
+        assert lens[4096] >= (n + 3) // 4 - 1                                            # every 4th row but itself
+        assert (idx < 0).any() and (idx == np.arange(n)[:, None]).any()
+        assert any(len(set(r[r >= 0])) < (r >= 0).sum() for r in idx)
+        bad = sc.carry_zero(rowptr)
+        assert np.array_equal(bad[:4096], rowptr[:4096]) and (bad[4096:] != rowptr[4096:]).all() and bad[4096] == 0
+        rows = np.repeat(np.arange(n), lens)
+        assert (np.diff(aff["col"].astype(np.int64) + rows * n) > 0).all()               # columns ascend inside a row
+    assert len(sc.affinity_sparse(cases["scan_8200"])["rowptr"]) == 8201
+    for name in ("hub", "ragged"):                                                       # one tile: the mistake cannot show
+        rowptr = sc.affinity(sc.list_cases()[name])["rowptr"]
+        assert np.array_equal(sc.carry_zero(rowptr), rowptr)
+
+
 # ------------------------------------------------------------------------------------------------- ABI, CLI, workspace
 def test_abi_declares_the_graph_entry_points():
     from scd_amd import _lib

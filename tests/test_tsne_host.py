@@ -1,6 +1,7 @@
 """CPU checks of the numpy restatement tests/tsne_cases.py that the GPU tests of t-SNE compare the device against: calibration against
 scipy's brentq roots, the joint matrix, the gradient, KL, the optimiser, the PCA start and trustworthiness against scikit-learn 1.7,
-and every planted mistake of tsne_cases.MISTAKES against the bound of the test that is meant to catch it.  docs/design/tsne.md."""
+and every planted mistake of tsne_cases.MISTAKES and RANGE_MISTAKES against the bound of the test that is meant to catch it; the range
+rule, banded_p and the torch restatement of the cases whose column ranges hold several chunks.  docs/design/tsne.md."""
 import os
 
 import numpy as np
@@ -175,6 +176,133 @@ def test_the_device_bound_catches_a_column(n):
         if n == 1023 and state == "converged":                                          # the helper is the restatement's own column
             F2, z2, _ = tc.repulsion_f64(Y, drop_column=j)
             assert np.allclose(F2, F - np.stack([tx, ty], 1), rtol=0, atol=1e-12 * MF.max()) and np.allclose(z2, z - q, rtol=1e-12)
+
+
+# ------------------------------------------------------------------------------------------------- ranges of several chunks
+def test_ranges_of_the_large_cases():
+    """The figures the large cases are named for, from the restated rule alone: 33 and 50 chunks, on 64, 256 and 304 compute units."""
+    c33, c50 = tc.LARGE["c33"], tc.LARGE["c50"]
+    assert (tc.cdiv(c33, tc.CHUNK), tc.cdiv(c50, tc.CHUNK)) == (33, 50) and c33 % tc.CHUNK == 1 and c50 % tc.CHUNK == 1
+    assert tc.ranges(c33 - 1, 256) == (32, 1, 1)                                        # c33 is the smallest n that reaches the path
+    assert tc.ranges(c33, 256) == (17, 2, 1) and tc.ranges(c33, 304) == (17, 2, 1) and tc.ranges(c33, 64) == (7, 5, 3)
+    assert tc.ranges(c50, 256) == (17, 3, 2) and tc.ranges(c50, 304) == (25, 2, 2) and tc.ranges(c50, 64) == (6, 9, 5)
+    assert tc.ranges(3001, 256) == (3, 1, 1) and tc.ranges(2, 256) == (1, 1, 1)         # the earlier cases: one chunk a range
+    for n in tc.LARGE.values():
+        for n_cu in range(1, 1025):
+            ny, cpy, last = tc.ranges(n, n_cu)
+            assert cpy >= 2 and 1 <= last <= cpy and (ny - 1) * cpy + last == tc.cdiv(n, tc.CHUNK) and ny <= tc.YMAX
+    assert set(tc.LARGE_STATES["c33"]) == set(tc.STATES) and tc.LARGE_STATES["c50"] == ("converged", "coincident")
+
+
+TORCH_RTOL = 1e-13              # repulsion_f64_torch against repulsion_f64: float64 sums of the same terms in another order
+
+
+def test_torch_restatement_equals_numpy():
+    n = 3001
+    worst_f = worst_z = 0.0
+    for state in tc.STATES:
+        Y = tc.state(state, n)
+        F, z, MF = tc.repulsion_f64(Y)
+        Ft, zt, MFt = tc.repulsion_f64_torch(Y, device="cpu")
+        with np.errstate(divide="ignore", invalid="ignore"):
+            worst_f = max(worst_f, float(np.nanmax(np.where(MF > 0, np.abs(Ft - F) / MF, 0.0))))
+        worst_z = max(worst_z, float((np.abs(zt - z) / z).max()))
+        assert (np.abs(Ft - F) <= TORCH_RTOL * MF).all() and (np.abs(MFt - MF) <= TORCH_RTOL * MF).all(), state
+        assert (np.abs(zt - z) <= TORCH_RTOL * z).all(), state
+        if state == "coincident":
+            assert (zt == n - 1).all() and not Ft.any()
+    print("torch against numpy at n = %d: forces within %.2e M_i, q sums within %.2e z_i" % (n, worst_f, worst_z))
+    rows = np.array([0, 7, 3000])
+    Y = tc.state("converged", n)
+    F, z, MF = tc.repulsion_f64(Y)
+    Fr, zr, MFr = tc.repulsion_f64(Y, rows=rows)                                         # rows= is a slice of the same sums
+    assert np.array_equal(Fr, F[rows]) and np.array_equal(zr, z[rows]) and np.array_equal(MFr, MF[rows])
+
+
+def test_banded_p():
+    import time
+    t0 = time.perf_counter()
+    big = tc.banded_p(tc.LARGE["c50"], seed=11)
+    took = time.perf_counter() - t0
+    print("banded_p at n = %d: %d entries, row 0 has %d, %.3f s" % (tc.LARGE["c50"], len(big[1]), big[0][1], took))
+    for n, P in ((3001, tc.banded_p(3001, seed=11)), (tc.LARGE["c33"], tc.banded_p(tc.LARGE["c33"], seed=11)), (tc.LARGE["c50"], big)):
+        indptr, indices, values = P
+        rows = np.repeat(np.arange(n, dtype=np.int64), np.diff(indptr))
+        cols = indices.astype(np.int64)
+        assert indptr[-1] == len(indices) == len(values) and (values > 0).all() and (rows != cols).all()
+        assert (np.diff(rows * n + cols) > 0).all()                                      # rows in order, columns ascending, no repeat
+        back = np.argsort(cols * n + rows, kind="stable")                               # the transpose in the same order
+        assert np.array_equal(rows[back], cols) and np.array_equal(cols[back], rows) and np.array_equal(values[back], values)
+        assert abs(values.sum() - 1.0) <= 1e-12
+        assert indptr[1] - indptr[0] > 192                                               # more than three trips of the lane loop
+        assert len(np.unique(indices[:indptr[1]] // tc.CHUNK)) == tc.cdiv(n, tc.CHUNK)   # the hub reaches every chunk
+        other = np.zeros(n, dtype=bool)
+        other[rows[cols // tc.CHUNK != rows // tc.CHUNK]] = True
+        assert other[:tc.ROWS].all()                                                     # every row of the first tile leaves its chunk
+        assert (np.diff(indptr) >= 4).all()
+
+
+@pytest.fixture(scope="module")
+def range_sums():
+    """state -> (Y, rows, F, z, MF) on c33: the float64 sums over all columns of the 64 rows."""
+    n = tc.LARGE["c33"]
+    rows = tc.range_rows(n)
+    out = {}
+    for state in ("converged", "coincident"):
+        Y = tc.state(state, n)
+        out[state] = (Y, rows) + tc.repulsion_f64(Y, rows=rows)
+    return out
+
+
+def test_range_rows():
+    rows = tc.range_rows(tc.LARGE["c33"])
+    assert len(rows) == len(set(rows.tolist())) == 64 and {0, 1023, 1024, 2047, 2048, 32767, 32768} <= set(rows.tolist())
+    assert len(tc.RANGE_MISTAKES) == 4
+
+
+@pytest.mark.parametrize("n_cu", [64, 256, 304])
+@pytest.mark.parametrize("mistake", tc.RANGE_MISTAKES)
+def test_range_mistakes_exceed_the_bound(range_sums, mistake, n_cu):
+    """Each planted mistake of the chunk loop and the range sum moves a force of one of the 64 rows by more than the device bound on
+    `converged`, and a q sum by a whole number on `coincident`, where every term is exactly 1 or 0."""
+    u = 2.0 ** -24
+    n = tc.LARGE["c33"]
+    Y, rows, F, z, MF = range_sums["converged"]
+    dF, dz = tc.range_mistake_shift(Y, rows, n_cu, mistake)
+    over = np.abs(dF) > tc.C_BOUND * u * MF
+    print("%s on %d CUs, converged: %d of 64 rows over the bound, largest shift %.3g x 2^-24 M_i" % (mistake, n_cu, over.any(1).sum(), (np.abs(dF) / (u * MF)).max()))
+    assert over.any(), (mistake, n_cu)
+    Y, rows, F, z, MF = range_sums["coincident"]
+    assert (z == n - 1).all() and not F.any()
+    dF, dz = tc.range_mistake_shift(Y, rows, n_cu, mistake, padding=False)              # the rows' own columns: every term is 1 or 0
+    assert not dF.any() and np.array_equal(dz, np.round(dz)) and (np.abs(dz) >= 1).any(), (mistake, n_cu)
+    lost, extra = tc.dropped_columns(n, n_cu, 1024, mistake)
+    assert (extra < n).sum() - len(lost) == dz[list(rows).index(1024)]
+
+
+def test_dropped_columns_by_hand():
+    """The model on c33 with 256 compute units, 17 ranges of 2 and a last range of one chunk with ONE column, worked by hand."""
+    n = tc.LARGE["c33"]
+    lost, extra = tc.dropped_columns(n, 256, 5, "first_chunk_only")                     # the odd chunks, all full
+    assert len(extra) == 0 and len(lost) == 16 * 1024 and lost[0] == 1024 and lost[-1] == 32767
+    lost, extra = tc.dropped_columns(n, 256, 1500, "first_chunk_only")                  # its own column is in an odd chunk
+    assert len(lost) == 16 * 1024 - 1 and 1500 not in lost
+    assert tc.dropped_columns(n, 256, 5, "last_range_dropped")[0].tolist() == [32768]
+    assert len(tc.dropped_columns(n, 256, 32768, "last_range_dropped")[0]) == 0         # the lone row of the last tile loses nothing
+    lost, extra = tc.dropped_columns(n, 256, 5, "stale_range")
+    assert len(lost) == 0 and len(extra) == 2047 and 5 not in extra
+    assert len(tc.dropped_columns(tc.LARGE["c50"], 304, 5, "stale_range")[1]) == 0      # 25 ranges before and after
+    for row, want in ((0, ([1024], [])), (1023, ([2047], [])), (1024, ([], [1024])), (2047, ([], [2047])), (2048, ([3072], [])),
+                      (32767, ([], [32767])), (32768, ([], []))):
+        lost, extra = tc.dropped_columns(n, 256, row, "own_chunk_unchecked")
+        assert (lost.tolist(), extra.tolist()) == want, row
+    # 64 compute units: 7 ranges of 5, the last one chunks 30, 31 and 32; chunk 32 stops after its first run of 64
+    lost, extra = tc.dropped_columns(n, 64, 5, "own_chunk_unchecked")
+    assert lost.tolist() == [1029, 2053, 3077, 4101] and extra.tolist() == list(range(n, n + 63))      # its block of the last range
+    lost, extra = tc.dropped_columns(n, 64, 31 * 1024 + 7, "own_chunk_unchecked")
+    assert len(lost) == 0 and extra.tolist() == [31 * 1024 + 7] + list(range(n, n + 63))
+    lost, extra = tc.dropped_columns(n, 64, 30 * 1024 + 7, "own_chunk_unchecked")       # own chunk first: offset 7 of chunk 32 is padding
+    assert lost.tolist() == [31 * 1024 + 7] and extra.tolist() == [j for j in range(n, n + 63) if j != 32 * 1024 + 7]
 
 
 def sklearn_descent(P, y0, max_iter, mistake=None):

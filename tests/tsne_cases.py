@@ -1,7 +1,9 @@
 """A numpy float64 restatement of scd_tsne_calibrate / scd_tsne_gradient / scd_tsne_update and of scd_amd.tsne (include/scd_hip.h,
 docs/design/tsne.md), the named cases of the t-SNE tests and planted mistakes.
 
-Every function takes `mistake`: one of MISTAKES plants the named error, so that a test can show its bound would catch it."""
+Every function takes `mistake`: one of MISTAKES plants the named error, so that a test can show its bound would catch it.  The cases
+of more than 32 column chunks (LARGE) come with the host's range rule restated (ranges), a P built without n x n arrays (banded_p), the
+float64 sums in torch (repulsion_f64_torch) and the mistakes of the chunk loop and the range sum (RANGE_MISTAKES, dropped_columns)."""
 import os
 
 import numpy as np
@@ -117,20 +119,22 @@ def dense_csr(M):
 
 
 # ---------------------------------------------------------------------------------------------------- gradient
-def repulsion_f64(Y, mistake=None, drop_column=None, rows_per_step=512):
+def repulsion_f64(Y, mistake=None, drop_column=None, rows_per_step=512, rows=None):
     """Per row i the float64 sums over j != i of (q^2 dx, q^2 dy, q) as F [n, 2], z [n], and the sums of the terms' magnitudes MF [n, 2]
-    (Mz = z).  Y is taken as given (float32 values in float64 arithmetic)."""
+    (Mz = z).  Y is taken as given (float32 values in float64 arithmetic).  rows (optional, int [m]): only these rows, outputs [m, ..]."""
     Y = np.asarray(Y).astype(np.float64)
     n = Y.shape[0]
-    F, MF, z = np.zeros((n, 2)), np.zeros((n, 2)), np.zeros(n)
+    rows = np.arange(n) if rows is None else np.asarray(rows, dtype=np.int64)
+    m = len(rows)
+    F, MF, z = np.zeros((m, 2)), np.zeros((m, 2)), np.zeros(m)
     cols = Y if mistake != "padding_column" else np.concatenate([Y, np.zeros((1, 2))])       # a padding column sits at (0, 0)
-    for a in range(0, n, rows_per_step):
-        b = min(n, a + rows_per_step)
-        dx = Y[a:b, None, 0] - cols[None, :, 0]
-        dy = Y[a:b, None, 1] - cols[None, :, 1]
+    for a in range(0, m, rows_per_step):
+        b = min(m, a + rows_per_step)
+        dx = Y[rows[a:b], None, 0] - cols[None, :, 0]
+        dy = Y[rows[a:b], None, 1] - cols[None, :, 1]
         q = 1.0 / (1.0 + dx * dx + dy * dy)
         if mistake != "self_in_z":
-            q[np.arange(b - a), np.arange(a, b)] = 0.0
+            q[np.arange(b - a), rows[a:b]] = 0.0
         if drop_column is not None:
             q[:, drop_column] = 0.0
         t = q * q
@@ -138,6 +142,27 @@ def repulsion_f64(Y, mistake=None, drop_column=None, rows_per_step=512):
         MF[a:b, 0], MF[a:b, 1] = (t * np.abs(dx)).sum(1), (t * np.abs(dy)).sum(1)
         z[a:b] = q.sum(1)
     return F, z, MF
+
+
+def repulsion_f64_torch(Y, device="cpu", rows_per_step=256):
+    """repulsion_f64's sums (F, z, MF as numpy float64) in float64 torch operations over blocks of rows, on `device`: the float64 answer
+    at sizes where numpy takes a minute per state.  Plain elementwise operations and row sums; nothing of scd_amd."""
+    import torch
+    y = torch.as_tensor(np.ascontiguousarray(Y)).to(device=device, dtype=torch.float64)
+    n = y.shape[0]
+    cx, cy = y[:, 0].contiguous()[None, :], y[:, 1].contiguous()[None, :]
+    F, MF = torch.zeros((n, 2), dtype=torch.float64, device=device), torch.zeros((n, 2), dtype=torch.float64, device=device)
+    z = torch.zeros(n, dtype=torch.float64, device=device)
+    for a in range(0, n, rows_per_step):
+        b = min(n, a + rows_per_step)
+        dx, dy = y[a:b, 0:1] - cx, y[a:b, 1:2] - cy
+        q = 1.0 / (1.0 + dx * dx + dy * dy)
+        q[torch.arange(b - a, device=device), torch.arange(a, b, device=device)] = 0.0
+        t = q * q
+        F[a:b, 0], F[a:b, 1] = (t * dx).sum(1), (t * dy).sum(1)
+        MF[a:b, 0], MF[a:b, 1] = (t * dx.abs()).sum(1), (t * dy.abs()).sum(1)
+        z[a:b] = q.sum(1)
+    return F.cpu().numpy(), z.cpu().numpy(), MF.cpu().numpy()
 
 
 def column_terms(Y, col):
@@ -303,6 +328,129 @@ def sparse_p(n, seed, per_row=6):
         M[i, js] = r.uniform(0.5, 1.5, size=len(js))
     M = M + M.T
     return dense_csr(M / M.sum())
+
+
+# ---------------------------------------------------------------------------------------------------- ranges of several chunks
+ROWS = CHUNK = 1024             # scd_tsne_row_tile(), scd_tsne_col_chunk()
+RUN = 64                        # columns per fp32 run: a chunk stops after the run in which the columns end
+YMAX = 32                       # the most column ranges
+
+
+def cdiv(a, b):
+    return -(-a // b)
+
+
+def ranges(n, n_cu):
+    """scd_tsne_gradient's split of the column chunks into ranges on a device of n_cu compute units, restated:
+    (ny, chunks_per_y, chunks in the last range)."""
+    chunks, tiles = cdiv(n, CHUNK), cdiv(n, ROWS)
+    ny = max(1, min(cdiv(4 * n_cu, tiles), min(chunks, YMAX)))
+    chunks_per_y = cdiv(chunks, ny)
+    ny = cdiv(chunks, chunks_per_y)                             # no empty range
+    return ny, chunks_per_y, chunks - (ny - 1) * chunks_per_y
+
+
+# n of the cases whose ranges hold several chunks on every device (chunks > YMAX): 33 chunks, the last chunk and the last row tile with
+# ONE valid row; 50 chunks, the same
+LARGE = {"c33": 32769, "c50": 50177}
+LARGE_STATES = {"c33": ("initial", "converged", "coincident", "pairs", "outlier"), "c50": ("converged", "coincident")}
+
+
+def banded_p(n, hub_links=200, seed=0):
+    """A symmetric CSR P with positive entries summing to 1, built without an n x n array: row i links to i +- 1, i +- 2, i +- 1024 and
+    i +- 1025 (its own chunk and the next), and row 0 to hub_links more rows spread over all chunks, so its entries take the attract
+    kernel's lane loop (64 entries a trip) round more than three times."""
+    r = np.random.RandomState(seed)
+    i = np.arange(n, dtype=np.int64)
+    lo = [i[:n - o] for o in (1, 2, CHUNK, CHUNK + 1) if o < n]
+    hi = [i[o:] for o in (1, 2, CHUNK, CHUNK + 1) if o < n]
+    spread = 3 + (np.arange(hub_links, dtype=np.int64) * (n - 4)) // max(hub_links - 1, 1)  # from column 3 to column n - 1, ascending
+    lo.append(np.zeros(len(spread), dtype=np.int64))
+    hi.append(spread)
+    keys = np.unique(np.concatenate(lo) * n + np.concatenate(hi))                           # the pairs i < j, each once
+    w = r.uniform(0.5, 1.5, size=len(keys))
+    a, b = keys // n, keys - (keys // n) * n
+    rows, cols, vals = np.concatenate([a, b]), np.concatenate([b, a]), np.concatenate([w, w])
+    order = np.argsort(rows * n + cols, kind="stable")
+    rows, cols, vals = rows[order], cols[order], vals[order]
+    indptr = np.zeros(n + 1, dtype=np.int64)
+    indptr[1:] = np.cumsum(np.bincount(rows, minlength=n))
+    return indptr, cols.astype(np.int32), vals / vals.sum()
+
+
+RANGE_MISTAKES = ("first_chunk_only", "last_range_dropped", "stale_range", "own_chunk_unchecked")
+
+
+def dropped_columns(n, n_cu, row, mistake):
+    """What a tsne_repulse_kernel / tsne_finish_kernel pair with one of RANGE_MISTAKES gets wrong in the sums of `row` on a device of n_cu
+    compute units: (lost, extra), int64 arrays of column indices.  `lost` columns' terms are missing.  `extra` columns' terms are counted
+    once more than they should be: a column j != row a second time, j == row the self pair (q = 1, no force), j >= n a padding column,
+    which sits at the origin.
+
+    first_chunk_only     a block stops after the first chunk of its range (the chunk loop never makes its second trip)
+    last_range_dropped   the sum over the ranges stops one short
+    stale_range          the sum runs over the range count from BEFORE the 'no empty range' step: partial sums that no block wrote.  What
+                         they hold is arbitrary; the model is a second copy of range 0's sums.  Nothing when the step changes nothing.
+    own_chunk_unchecked  a block decides `check` and the index it excludes once, at the first chunk of its range.  First chunk foreign
+                         and full: the later chunks run unchecked, so the own chunk counts the self pair and the last chunk its padding
+                         columns up to the end of the run of 64.  First chunk the tile's own: in every later chunk the column at the row's
+                         offset is excluded in place of the row, and the padding columns pass `col < n`."""
+    ny, cpy, _ = ranges(n, n_cu)
+    chunks, tile, off = cdiv(n, CHUNK), row // ROWS, row % ROWS
+    stop = lambda ch: min((ch + 1) * CHUNK, cdiv(n, RUN) * RUN)                              # where the chunk's column loop ends
+    real = lambda cols: cols[(cols < n) & (cols != row)]
+    span = lambda a, b: np.arange(a * CHUNK, min(b, chunks) * CHUNK, dtype=np.int64)
+    none = np.zeros(0, dtype=np.int64)
+    if mistake == "first_chunk_only":
+        return real(np.concatenate([span(y * cpy + 1, (y + 1) * cpy) for y in range(ny)])), none
+    if mistake == "last_range_dropped":
+        return real(span((ny - 1) * cpy, chunks)), none
+    if mistake == "stale_range":
+        before = max(1, min(cdiv(4 * n_cu, cdiv(n, ROWS)), min(chunks, YMAX)))
+        return none, (real(span(0, cpy)) if before > ny else none)
+    if mistake == "own_chunk_unchecked":
+        lost, extra = [], []
+        for y in range(ny):
+            first, last = y * cpy, min((y + 1) * cpy, chunks)
+            if first == tile:
+                for ch in range(first + 1, last):
+                    j = ch * CHUNK + off
+                    if j < n:
+                        lost.append(j)
+                    pad = np.arange(max(n, ch * CHUNK), stop(ch), dtype=np.int64)
+                    extra.extend(pad[pad != j].tolist())
+            elif (first + 1) * CHUNK <= n:                      # foreign and full: unchecked from here on
+                for ch in range(first + 1, last):
+                    if ch == tile:
+                        extra.append(row)
+                    extra.extend(range(max(n, ch * CHUNK), stop(ch)))
+        return np.array(lost, dtype=np.int64), np.array(extra, dtype=np.int64)
+    raise KeyError(mistake)
+
+
+def range_mistake_shift(Y, rows, n_cu, mistake, padding=True):
+    """(dF [m, 2], dz [m]): by how much `mistake` moves the float64 sums of `rows` (dropped_columns' terms, extra minus lost);
+    padding=False leaves the padding columns out, whose terms are no whole numbers when all rows coincide."""
+    Y = np.asarray(Y).astype(np.float64)
+    n = Y.shape[0]
+    cols = np.concatenate([Y, np.zeros((cdiv(n, RUN) * RUN - n, 2))])                       # the padding columns sit at (0, 0)
+    dF, dz = np.zeros((len(rows), 2)), np.zeros(len(rows))
+    for m, i in enumerate(rows):
+        for sign, js in zip((-1.0, 1.0), dropped_columns(n, n_cu, int(i), mistake)):
+            js = js if padding else js[js < n]
+            dx, dy = Y[i, 0] - cols[js, 0], Y[i, 1] - cols[js, 1]
+            q = 1.0 / (1.0 + dx * dx + dy * dy)
+            dF[m] += sign * np.array([(q * q * dx).sum(), (q * q * dy).sum()])
+            dz[m] += sign * q.sum()
+    return dF, dz
+
+
+def range_rows(n, seed=81, seeded=57):
+    """The rows of the sensitivity test: the first and last rows of the first tiles, the last full tile's last row, the lone row of the
+    last tile, and `seeded` others."""
+    fixed = [0, ROWS - 1, ROWS, 2 * ROWS - 1, 2 * ROWS, n - 2, n - 1]
+    others = np.setdiff1d(np.arange(n), fixed)
+    return np.array(fixed + sorted(np.random.RandomState(seed).choice(others, size=seeded, replace=False).tolist()), dtype=np.int64)
 
 
 STATES = ("initial", "converged", "coincident", "pairs", "outlier")
