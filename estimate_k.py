@@ -4,18 +4,22 @@ to for an unknown class number) on the feature caches main_unsup.py / main_ptsup
   ROOT/extracted_features/{feat_model}_{dataset_name}_all.pt     dict all_feats, mask_lab, targets (main_unsup.py:141-146)
 
 All features, labelled and unlabelled, are L2-normalised once (estimate_k.py:61) and clustered with
-`KMeans(n_clusters=K, random_state=0)` for the Ks a search asks for.  Two criteria:
+`KMeans(n_clusters=K, random_state=0)` for the Ks a search asks for.  Three criteria:
 
   --criterion acc (default)   GCD's: the K with the highest clustering accuracy on the LABELLED rows wins; bounded Brent search
                               (default, :221-242) or the reference's binary search (:172-218).  Needs labelled rows.
   --criterion silhouette      label-free: the K with the highest mean silhouette coefficient over all rows wins; integer grid search
                               by default.  For caches without labelled rows (main_unsup.py's setting).
+  --criterion bic             label-free: a diagonal Gaussian mixture of K components (scd_amd.gmm, --covariance_type) is fitted
+                              instead of k-means and the K with the LOWEST Bayesian information criterion wins; integer grid search
+                              by default.  One n x K x d pass per EM step and no n x n pass; K <= 1024, d <= 1024.
 
 Fits and scores run on the GPU (scd_amd.cluster.KMeans, scd_amd.metrics).  Writes
 ROOT/cluster/estimated_k_{feat_model}_{dataset_name}.json and prints the value to pass as --n_cluster.
 
   python estimate_k.py --root_dir ROOT --dataset_name cub --feat_model clip [--max_classes 1000] [--search_mode brent|binary|grid|finch]
   python estimate_k.py --root_dir ROOT --dataset_name D --feat_model clip --criterion silhouette --max_classes 1000
+  python estimate_k.py --root_dir ROOT --dataset_name D --feat_model clip --criterion bic --max_classes 200 [--covariance_type spherical]
 """
 import argparse
 import json
@@ -36,11 +40,13 @@ def build_parser():
     p.add_argument('--max_classes', default=1000, type=int)
     p.add_argument('--min_classes', default=None, type=int,
                    help='default: acc - the number of distinct targets among the labelled rows (the reference\'s num_labeled_classes); '
-                        'silhouette - 2')
-    p.add_argument('--criterion', type=str, default='acc', choices=['acc', 'silhouette'],
-                   help='acc: clustering accuracy on the labelled rows (GCD); silhouette: mean silhouette coefficient, needs no labels')
+                        'silhouette and bic - 2')
+    p.add_argument('--criterion', type=str, default='acc', choices=['acc', 'silhouette', 'bic'],
+                   help='acc: clustering accuracy on the labelled rows (GCD); silhouette: mean silhouette coefficient, needs no labels; '
+                        'bic: lowest Bayesian information criterion of a diagonal Gaussian mixture, needs no labels')
+    p.add_argument('--covariance_type', type=str, default='diag', choices=['diag', 'spherical'], help="--criterion bic: the mixture's covariances")
     p.add_argument('--search_mode', type=str, default=None, choices=['brent', 'binary', 'grid', 'finch'],
-                   help='Mode for black box optimisation; default: brent for acc, grid for silhouette.  finch: score only the '
+                   help='Mode for black box optimisation; default: brent for acc, grid for silhouette and bic.  finch: score only the '
                         'cluster counts of FINCH\'s partitions of all rows, clipped to [min_classes, max_classes]')
     return p
 
@@ -50,7 +56,7 @@ def parse_args(argv=None):
     args = build_parser().parse_args(argv)
     if args.search_mode is None:
         args.search_mode = 'brent' if args.criterion == 'acc' else 'grid'
-    if args.min_classes is None and args.criterion == 'silhouette':
+    if args.min_classes is None and args.criterion in ('silhouette', 'bic'):
         args.min_classes = 2
     return args
 
@@ -63,13 +69,16 @@ def main(argv=None):
     data = torch.load(path, weights_only=False)
     mask_lab = np.asarray(data['mask_lab']).astype(bool)
     targets = np.asarray(data['targets']).astype(int)
-    sil = args.criterion == 'silhouette'
-    if not sil and not mask_lab.any():
+    sil, bic = args.criterion == 'silhouette', args.criterion == 'bic'
+    if not sil and not bic and not mask_lab.any():
         raise SystemExit("the cache has no labelled row: the estimator scores K on the labelled rows")
     feats = ops.l2norm_rows(torch.as_tensor(np.asarray(data['all_feats'])).to(dev).float())
     if sil:
         small_k = args.min_classes
         big_k = min(args.max_classes, feats.shape[0] - 1)       # the silhouette needs fewer clusters than rows
+    elif bic:
+        small_k = args.min_classes
+        big_k = min(args.max_classes, feats.shape[0], 1024)     # the mixture kernel's limit on K
     else:
         small_k = args.min_classes if args.min_classes is not None else len(np.unique(targets[mask_lab]))
         big_k = min(args.max_classes, feats.shape[0])
@@ -83,6 +92,11 @@ def main(argv=None):
             s, scores[int(K)] = ek.evaluate_k_unlabelled(K, feats, verbose=True)
             return s
         name = 'silhouette'
+    elif bic:
+        def evaluate(K):                                        # the searches maximise: -BIC; scores[K] keeps the BIC and the lower bound
+            s, scores[int(K)] = ek.evaluate_k_bic(K, feats, covariance_type=args.covariance_type, verbose=True)
+            return s
+        name = 'neg_bic'
     else:
         targets_dev = torch.as_tensor(targets, device=dev)
         mask_dev = torch.as_tensor(mask_lab, device=dev)

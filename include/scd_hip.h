@@ -511,6 +511,44 @@ int scd_probe_loss_grad(scd_handle h, const float* X, const int32_t* y, const fl
 int scd_probe_predict(scd_handle h, const float* X, int64_t n, int d, int c, const float* W, const float* b, int32_t* pred_out,
                       float* top_logit_out, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- Gaussian mixtures with diagonal covariances: scikit-learn 1.7's GaussianMixture(covariance_type='diag' | 'spherical'), with
+ *      labelled rows clamped to their class (the semi-supervised mixture of GPC, "Learning semi-supervised Gaussian mixture models for
+ *      generalized category discovery"; docs/design/gmm.md) ---- */
+/* Bytes of workspace of scd_gmm_em_step for X [n, d] and k components: the packed B and C, the responsibilities r float32 [n, k up to
+ * 32], the row log-likelihoods float64 [n] and the float64 partial sums of the row ranges; 0.66 GB at n = 126,976, d = 768, k = 1000.
+ * 0 outside the limits 1 <= n < 2^31, 1 <= d <= 1024, 1 <= k <= 1024.  scd_gmm_predict needs scd_gmm_ws_bytes(1, d, k) whatever its n. */
+size_t scd_gmm_ws_bytes(int64_t n, int d, int k);
+/* Rows of X a block of the forward kernel owns (with all k components). */
+int scd_gmm_row_tile(void);
+/* The longest float32 accumulation chain over rows in the moments (<= 1024): a chain's 32 x 32 tile is added into float64, so a
+ * moment's rounding error is gamma_T sum_i |r_ik x_id| with T this value, whatever n. */
+int scd_gmm_chain_rows(void);
+/* One E-step and the sufficient statistics of the M-step at the weighted log-densities
+ *   z_ik = a_k + sum_d x_id B_kd + sum_d x_id^2 C_kd,   B = mu / v,  C = -1 / (2 v),
+ *   a_k = log w_k - 0.5 sum_d mu_kd^2 / v_kd - 0.5 sum_d log v_kd - (d / 2) log 2 pi
+ * (the caller forms them in float64 and rounds to float32; a constant may be taken out of a and added back to ll, the softmax does not
+ * see it).  X float32 [n, d]; y int32 [n] or NULL; a float32 [k]; B, C float32 [k, d]; s_i = sample_weight[i], or 1 when it is NULL.
+ *   an unlabelled row (y NULL, or y_i < 0):  r_ik = s_i softmax_k(z_i),  row log-likelihood s_i lse_k(z_ik)
+ *   a labelled row (0 <= y_i < k):           r_ik = s_i [k == y_i],      row log-likelihood s_i z_{i,y_i}   (the clamped E-step)
+ *   y_i >= k:                                the row is unlabelled, and info[0] counts it
+ * ll_out double [1] = the sum of the row log-likelihoods, nk_out double [k] = sum_i r_ik, s1_out double [k, d] = r^T X, s2_out double
+ * [k, d] = r^T (X o X); pred_out int32 [n] or NULL: argmax_k z_ik of every row whatever its label, ties to the lowest component.
+ * info_out int32 [2] = {rows with y_i >= k; rows with a non-finite logit: the outputs are then not meaningful}.
+ * a == B == C == NULL is the hard M-step (y is then required): no density pass runs, every row with a label in range contributes its
+ * one-hot times s_i, every other row nothing, ll_out is 0 and pred_out is not written.
+ * The logits are float32 fma chains from a zero accumulator (the float32-input MFMA): octets of d ascending, within an octet the eight
+ * x B products, then the eight x^2 C products (x^2 one float32 multiply), a_k added last; the softmax uses expf / logf and a correctly
+ * rounded division on z - max, the maximum over the real components; the moments accumulate float32 over chains of
+ * scd_gmm_chain_rows() rows and float64 across them.  No [n, k] logits reach memory, only r.  Two calls return the same bits: no
+ * floating-point atomics, and every partition of the work depends on (n, d, k) alone. */
+int scd_gmm_em_step(scd_handle h, const float* X, const int32_t* y, const float* sample_weight, int64_t n, int d, int k, const float* a,
+                    const float* B, const float* C, double* ll_out, double* nk_out, double* s1_out, double* s2_out, int32_t* pred_out,
+                    int32_t* info_out, void* ws, size_t ws_bytes, void* stream);
+/* The forward pass alone, the same logits as scd_gmm_em_step's: pred_out int32 [n] or NULL = argmax_k z_ik (ties to the lowest
+ * component), row_ll_out float32 [n] or NULL = lse_k z_ik, resp_out float32 [n, k] or NULL = softmax_k(z_i), dense. */
+int scd_gmm_predict(scd_handle h, const float* X, int64_t n, int d, int k, const float* a, const float* B, const float* C,
+                    int32_t* pred_out, float* row_ll_out, float* resp_out, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- exact t-SNE: scikit-learn 1.7's TSNE(n_components=2) as the reference's save_tsne / save_tsne_wcolor call it
  *      (local_utils/util.py:178-216), with the exact all-pairs gradient instead of Barnes-Hut's (docs/design/tsne.md) ---- */
 /* The conditional affinities of a k-NN graph: dist2 double [n, k] (squared distances, finite and >= 0), row i ->

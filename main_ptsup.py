@@ -76,7 +76,7 @@ def main(argv=None):
     cpath = os.path.join(cdir, f'{args.cluster}_{mu.feat_cache_name(args)}_{args.dataset_name}.pt')   # :385 (no n_cluster)
     if args.run_cluster or args.synthetic:
         print(f'Fitting {args.cluster} ...')
-        all_preds, preds = mu.run_clustering(args, u_feats, l_feats, l_targets)
+        all_preds, preds = mu.run_clustering(args, u_feats, l_feats, l_targets, semi_supervised=True)
         if all_preds is None:
             raise SystemExit("--cluster KM gives no labels for the labelled rows (all_preds), which the partially supervised vote "
                              "needs (main_ptsup.py:591-625): use SSKM or ConSSKM")

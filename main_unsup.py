@@ -7,7 +7,7 @@ Here every stage starts from the reference's own cache files under --root_dir, b
   extracted_features/{feat_model}_{dataset}_all.pt   dict all_feats, mask_lab, mask_cls, targets      (:141-146,294-301)
   extracted_features/clip_{dataset}_all.pt           same dict, CLIP features                          (:306-311)
   cluster/{cluster}_{feat_model}_{dataset}_{n_cluster}.pt   dict all_preds, u_preds, u_targets, mask  (:366-374)
-                                                            ({cluster} = KM, SSKM, ConSSKM, FINCH or SC)
+                                                            ({cluster} = KM, SSKM, ConSSKM, FINCH, SC or GMM)
   cluster/HDBSCAN_{feat_model}_{dataset}_mcs{min_cluster_size}[_ms{min_samples}].pt   the same dict plus noise, probabilities, n_cluster
                                                             (--cluster HDBSCAN: the number of clusters is a result, not a flag)
   zeroshot_weights/zeroshot_weights_all_{nouns|wikibird|wikidog}_vit_b_16.pt   tensor [512, V]        (:389-394)
@@ -65,7 +65,8 @@ def build_parser():
     p.add_argument('--run_cluster', type=str2bool, default=False)
     p.add_argument('--cluster', type=str, default='KM', help='options: KM, SSKM, ConSSKM, FINCH (first-neighbour clustering refined to --n_cluster clusters), '
                                                                      'SC (spectral clustering on the exact k-NN graph, see --n_neighbors), '
-                                                                     'HDBSCAN (no --n_cluster: the number of clusters is a result, see --min_cluster_size)')
+                                                                     'HDBSCAN (no --n_cluster: the number of clusters is a result, see --min_cluster_size), '
+                                                                     'GMM (a diagonal Gaussian mixture of --n_cluster components, see --covariance_type)')
     p.add_argument('--save_cluster', type=str2bool, default=False)
     p.add_argument('--n_cluster', type=int, default=1000)
     p.add_argument('--n_neighbors', type=int, default=10,
@@ -73,6 +74,8 @@ def build_parser():
     p.add_argument('--min_cluster_size', type=int, default=5, help="--cluster HDBSCAN: scikit-learn's min_cluster_size")
     p.add_argument('--min_samples', type=int, default=None,
                    help="--cluster HDBSCAN: scikit-learn's min_samples, the row itself included, 1 to 65 (default: min_cluster_size)")
+    p.add_argument('--covariance_type', type=str, default='diag', choices=['diag', 'spherical'],
+                   help="--cluster GMM: scikit-learn's covariance_type, a variance per component and dimension or one per component")
     p.add_argument('--cluster_size_min', type=int, default=50)
     p.add_argument('--cluster_size_max', type=int, default=1200)
     p.add_argument('--corpus', type=str, default='wordnet', help='options: wordnet, wikibird, wikidog')
@@ -92,8 +95,31 @@ def build_parser():
     return p
 
 
-def run_clustering(args, u_feats, l_feats, l_targets):
-    """main_unsup.py:334-364.  Returns (all_preds or None, u_preds numpy)."""
+def run_gmm(args, u_feats, l_feats=None, l_targets=None):
+    """--cluster GMM (docs/design/gmm.md): scd_amd.gmm.GaussianMixture(n_cluster, covariance_type, random_state=0).  Without labelled
+    rows it is fitted on the unlabelled rows, as KM is.  With them (main_ptsup.py) the labelled rows come first, each clamped to the
+    component of its class (the classes numbered in ascending order), and every row gets a label, as SSKM gives."""
+    from scd_amd.gmm import GaussianMixture
+    gm = GaussianMixture(n_components=args.n_cluster, covariance_type=args.covariance_type, random_state=0)
+    u = np.asarray(u_feats, dtype=np.float32)
+    if l_feats is None:
+        gm.fit(u)
+        print(f"GMM: {gm.n_iter_} iterations, converged {gm.converged_}, lower bound {gm.lower_bound_:.6f}, BIC {gm.bic(u):.1f}")
+        return None, gm.labels_
+    classes, y_l = np.unique(np.asarray(l_targets), return_inverse=True)
+    if len(classes) > args.n_cluster:
+        raise SystemExit(f"--cluster GMM: {len(classes)} labelled classes need --n_cluster >= {len(classes)} (got {args.n_cluster})")
+    x = np.concatenate([np.asarray(l_feats, dtype=np.float32), u])
+    y = np.concatenate([y_l.astype(np.int64), np.full(len(u), -1, dtype=np.int64)])
+    gm.fit(x, y)
+    print(f"GMM: {len(y_l)} rows clamped to {len(classes)} classes, {gm.n_iter_} iterations, converged {gm.converged_}, "
+          f"lower bound {gm.lower_bound_:.6f}")
+    return gm.labels_, gm.labels_[len(y_l):]
+
+
+def run_clustering(args, u_feats, l_feats, l_targets, semi_supervised=False):
+    """main_unsup.py:334-364.  Returns (all_preds or None, u_preds numpy).  semi_supervised: --cluster GMM clamps the labelled rows
+    (main_ptsup.py); the other methods ignore it."""
     dev = torch.device("cuda")
     if args.cluster == 'ConSSKM':
         km = ConSemiSupKMeans(k=args.n_cluster, tolerance=1e-4, max_iterations=10, init='k-means++', size_min=args.cluster_size_min,
@@ -115,6 +141,8 @@ def run_clustering(args, u_feats, l_feats, l_targets):
         from scd_amd.spectral import SpectralClustering
         sc = SpectralClustering(n_clusters=args.n_cluster, n_neighbors=args.n_neighbors, random_state=0)
         return None, sc.fit_predict(np.asarray(u_feats, dtype=np.float32)).astype(np.int64)
+    elif args.cluster == 'GMM':
+        return run_gmm(args, u_feats, l_feats, l_targets) if semi_supervised else run_gmm(args, u_feats)
     else:
         raise NotImplementedError(args.cluster)
     u, l, lt = (torch.as_tensor(x).to(dev) for x in (u_feats, l_feats, l_targets))

@@ -153,6 +153,13 @@ SIGNATURES = {
     "scd_probe_loss_grad": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     # h, X, n, d, c, W, b, pred_out, top_logit_out, ws, ws_bytes, stream
     "scd_probe_predict": (_i, [_vp, _vp, _i64, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "scd_gmm_ws_bytes": (_sz, [_i64, _i, _i]),
+    "scd_gmm_row_tile": (_i, []),
+    "scd_gmm_chain_rows": (_i, []),
+    # h, X, y, sample_weight, n, d, k, a, B, C, ll_out, nk_out, s1_out, s2_out, pred_out, info_out, ws, ws_bytes, stream
+    "scd_gmm_em_step": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    # h, X, n, d, k, a, B, C, pred_out, row_ll_out, resp_out, ws, ws_bytes, stream
+    "scd_gmm_predict": (_i, [_vp, _vp, _i64, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     # h, dist2, n, k, perplexity, p_out, beta_out, info_out, stream
     "scd_tsne_calibrate": (_i, [_vp, _vp, _i64, _i, C.c_double, _vp, _vp, _vp, _vp]),
     "scd_tsne_gradient_ws_bytes": (_sz, [_i64, _i64]),

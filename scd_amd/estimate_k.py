@@ -59,6 +59,21 @@ def evaluate_k_unlabelled(K, feats, verbose=False, **kmeans_kw):
     return s, {'silhouette': s}
 
 
+def evaluate_k_bic(K, feats, covariance_type="diag", verbose=False, **gmm_kw):
+    """One K of the mixture search: fit `GaussianMixture(n_components=K, covariance_type, random_state=0)` (scd_amd.gmm) on feats (device
+    float32 [n, d]) and take its BIC on the same rows: one n x K x d pass per EM step, no n x n pass.  The searches maximise, so the
+    value returned is -BIC: (-bic, {'bic', 'lower_bound', 'n_iter', 'converged'})."""
+    from .gmm import GaussianMixture
+    K = int(K)
+    kw = dict(random_state=0)
+    kw.update(gmm_kw)
+    gm = GaussianMixture(n_components=K, covariance_type=covariance_type, **kw).fit(feats)
+    bic = float(gm.bic(feats))
+    if verbose:
+        print('K = {}: BIC {:.1f}, lower bound {:.6f} ({} iterations)'.format(K, bic, gm.lower_bound_, gm.n_iter_))
+    return -bic, {'bic': bic, 'lower_bound': float(gm.lower_bound_), 'n_iter': int(gm.n_iter_), 'converged': bool(gm.converged_)}
+
+
 class _Memo:
     """evaluate(int K) -> float, each distinct K evaluated once."""
 

@@ -1109,6 +1109,73 @@ def probe_predict(x, w, b=None, want_top=False):
     return (pred, top) if want_top else pred
 
 
+# ----------------------------------------------------------------------------- Gaussian mixtures (docs/design/gmm.md)
+def _gmm_params(who, x, a, b, c):
+    _need_cuda(x, a, b, c)
+    if x.dim() != 2 or x.dtype != torch.float32:
+        raise _lib.ScdError(_lib.SCD_EINVAL, who + ": x float32 [n, d]")
+    k, d = a.shape[0] if a.dim() == 1 else -1, x.shape[1]
+    if any(t.dtype != torch.float32 for t in (a, b, c)) or k < 1 or b.shape != (k, d) or c.shape != (k, d):
+        raise _lib.ScdError(_lib.SCD_EINVAL, who + ": a float32 [k], b and c float32 [k, d]")
+    return x.contiguous(), a.contiguous(), b.contiguous(), c.contiguous()
+
+
+def gmm_em_step(x, a, b, c, y=None, sample_weight=None, want_pred=False, n_components=None):
+    """scd_gmm_em_step: x float32 [n, d]; a float32 [k], b = mu / v and c = -1 / (2 v) float32 [k, d] (the weighted log-density
+    z_ik = a_k + x_i . b_k + x_i^2 . c_k); y int32 [n] or None (a row with 0 <= y_i < k is clamped to its class, any other is
+    unlabelled); sample_weight float32 [n] or None -> (ll float64 [1], nk float64 [k], s1 float64 [k, d] = r^T x, s2 float64 [k, d] =
+    r^T x^2, pred int32 [n] or None, info int32 [2] = rows with y_i >= k, rows with a non-finite logit), all on the device.
+    With a = b = c = None and n_components = k it is the hard M-step: the labelled rows' one-hots alone, ll = 0, no pred."""
+    hard = a is None and b is None and c is None
+    if hard:
+        _need_cuda(x)
+        if x.dim() != 2 or x.dtype != torch.float32 or n_components is None or int(n_components) < 1 or y is None or want_pred:
+            raise _lib.ScdError(_lib.SCD_EINVAL, "gmm_em_step: the hard M-step takes x float32 [n, d], y, n_components >= 1 and no pred")
+        x, k = x.contiguous(), int(n_components)
+    else:
+        if a is None or b is None or c is None:
+            raise _lib.ScdError(_lib.SCD_EINVAL, "gmm_em_step: a, b and c are all given or all None")
+        x, a, b, c = _gmm_params("gmm_em_step", x, a, b, c)
+        k = a.shape[0]
+    n, d = x.shape
+    if y is not None:
+        _need_cuda(y)
+        if y.dtype != torch.int32 or y.shape != (n,):
+            raise _lib.ScdError(_lib.SCD_EINVAL, "gmm_em_step: y int32 [n]")
+        y = y.contiguous()
+    if sample_weight is not None:
+        _need_cuda(sample_weight)
+        if sample_weight.dtype != torch.float32 or sample_weight.shape != (n,):
+            raise _lib.ScdError(_lib.SCD_EINVAL, "gmm_em_step: sample_weight float32 [n]")
+        sample_weight = sample_weight.contiguous()
+    ll = torch.empty(1, dtype=torch.float64, device=x.device)
+    nk = torch.empty(k, dtype=torch.float64, device=x.device)
+    s1 = torch.empty((k, d), dtype=torch.float64, device=x.device)
+    s2 = torch.empty((k, d), dtype=torch.float64, device=x.device)
+    pred = torch.empty(n, dtype=torch.int32, device=x.device) if want_pred else None
+    info = torch.empty(2, dtype=torch.int32, device=x.device)
+    nb = _L().scd_gmm_ws_bytes(n, d, k)
+    ws = _ws(max(nb, 16), x.device)
+    check(_L().scd_gmm_em_step(handle(), ptr(x), ptr(y), ptr(sample_weight), n, d, k, ptr(a), ptr(b), ptr(c), ptr(ll), ptr(nk), ptr(s1),
+                               ptr(s2), ptr(pred), ptr(info), ptr(ws), nb, stream_ptr()))
+    return ll, nk, s1, s2, pred, info
+
+
+def gmm_predict(x, a, b, c, want_ll=False, want_resp=False):
+    """scd_gmm_predict: x float32 [n, d], a float32 [k], b and c float32 [k, d] -> (pred int32 [n] = argmax_k z_ik, ties to the lowest
+    component; row_ll float32 [n] = lse_k z_ik or None; resp float32 [n, k] = softmax_k(z_i) or None)."""
+    x, a, b, c = _gmm_params("gmm_predict", x, a, b, c)
+    (n, d), k = x.shape, a.shape[0]
+    pred = torch.empty(n, dtype=torch.int32, device=x.device)
+    row_ll = torch.empty(n, dtype=torch.float32, device=x.device) if want_ll else None
+    resp = torch.empty((n, k), dtype=torch.float32, device=x.device) if want_resp else None
+    nb = _L().scd_gmm_ws_bytes(1, d, k)
+    ws = _ws(max(nb, 16), x.device)
+    check(_L().scd_gmm_predict(handle(), ptr(x), n, d, k, ptr(a), ptr(b), ptr(c), ptr(pred), ptr(row_ll), ptr(resp), ptr(ws), nb,
+                               stream_ptr()))
+    return pred, row_ll, resp
+
+
 # ----------------------------------------------------------------------------- host solvers
 def munkres(cost):
     """linear_assignment (cluster_utils.py:234): int array [n,m] -> sorted pairs [min(n,m),2]."""
