@@ -20,6 +20,9 @@ ROOT/cluster/estimated_k_{feat_model}_{dataset_name}.json and prints the value t
   python estimate_k.py --root_dir ROOT --dataset_name cub --feat_model clip [--max_classes 1000] [--search_mode brent|binary|grid|finch]
   python estimate_k.py --root_dir ROOT --dataset_name D --feat_model clip --criterion silhouette --max_classes 1000
   python estimate_k.py --root_dir ROOT --dataset_name D --feat_model clip --criterion bic --max_classes 200 [--covariance_type spherical]
+
+--pca_dim M [--pca_whiten] reduces the normalised features to M principal components first (scd_amd.pca, docs/design/pca.md) and
+renormalises the rows; the mixture's responsibilities are informative there.
 """
 import argparse
 import json
@@ -48,6 +51,10 @@ def build_parser():
     p.add_argument('--search_mode', type=str, default=None, choices=['brent', 'binary', 'grid', 'finch'],
                    help='Mode for black box optimisation; default: brent for acc, grid for silhouette and bic.  finch: score only the '
                         'cluster counts of FINCH\'s partitions of all rows, clipped to [min_classes, max_classes]')
+    p.add_argument('--pca_dim', type=int, default=0,
+                   help='> 0: the normalised features are reduced to this many principal components (scd_amd.pca.PCA fitted on all rows) '
+                        'and renormalised to unit rows before the search; 0: off')
+    p.add_argument('--pca_whiten', action='store_true', help='--pca_dim: whiten the components before the renormalisation')
     return p
 
 
@@ -73,6 +80,11 @@ def main(argv=None):
     if not sil and not bic and not mask_lab.any():
         raise SystemExit("the cache has no labelled row: the estimator scores K on the labelled rows")
     feats = ops.l2norm_rows(torch.as_tensor(np.asarray(data['all_feats'])).to(dev).float())
+    if args.pca_dim:
+        from scd_amd.pca import PCA
+        pca = PCA(n_components=args.pca_dim, whiten=args.pca_whiten)
+        feats = pca.fit_transform(feats, unit=True)
+        print(f'PCA: {pca.n_components_} of {pca.n_features_in_} dimensions keep {pca.explained_variance_ratio_.sum():.4f} of the variance')
     if sil:
         small_k = args.min_classes
         big_k = min(args.max_classes, feats.shape[0] - 1)       # the silhouette needs fewer clusters than rows
@@ -125,6 +137,8 @@ def main(argv=None):
         out = dict(trace=[dict(ks=list(ks), scores=list(sc), best=int(b)) for ks, sc, b in trace])
     out.update(k=int(k), criterion=args.criterion, search_mode=args.search_mode, min_classes=int(small_k), max_classes=int(big_k),
                scores={str(kk): v for kk, v in sorted(scores.items())})
+    if args.pca_dim:
+        out.update(pca_dim=int(args.pca_dim), pca_whiten=bool(args.pca_whiten))
     cdir = os.path.join(args.root_dir, 'cluster')
     os.makedirs(cdir, exist_ok=True)
     jpath = os.path.join(cdir, f'estimated_k_{args.feat_model}_{args.dataset_name}.json')

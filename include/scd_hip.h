@@ -549,6 +549,35 @@ int scd_gmm_em_step(scd_handle h, const float* X, const int32_t* y, const float*
 int scd_gmm_predict(scd_handle h, const float* X, int64_t n, int d, int k, const float* a, const float* B, const float* C,
                     int32_t* pred_out, float* row_ll_out, float* resp_out, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- principal component analysis: scikit-learn 1.7's PCA(svd_solver='covariance_eigh') without a centred or float64 copy of the rows
+ *      (docs/design/pca.md).  Every call sees the rows as c_ij = fl32(x_ij - shift_j), one IEEE float32 subtraction in a register;
+ *      shift float32 [d], or NULL for 0.  The eigensolver of the d x d matrix is the caller's. ---- */
+/* Bytes of workspace for X [n, d] and m components: the float64 partial sums of the row ranges, a flag per row and the packed W; 0.15 GB
+ * at n = 126,976, d = 768, m = 1024.  0 outside the limits 1 <= n < 2^31, 1 <= d <= 1024, 1 <= m <= 1024.  scd_pca_colsum and
+ * scd_pca_gram need scd_pca_ws_bytes(n, d, 1), scd_pca_transform needs scd_pca_ws_bytes(1, d, m) whatever its n. */
+size_t scd_pca_ws_bytes(int64_t n, int d, int m);
+/* Rows of X a block of the projection kernel owns (with all m columns). */
+int scd_pca_row_tile(void);
+/* The longest float32 accumulation chain over rows in the Gram matrix: a chain's 32 x 32 tile is added into float64, so an element's
+ * rounding error is gamma_T sum_i |c_ij c_il| with T this value, whatever n. */
+int scd_pca_chain_rows(void);
+/* csum_out double [d] = sum_i c_ij in float64 (the subtraction alone is float32): row ranges of a fixed size, added in ascending order.
+ * With shift NULL it is n times the mean; with the rounded mean as shift it is the exact residual, which is not zero. */
+int scd_pca_colsum(scd_handle h, const float* X, const float* shift, int64_t n, int d, double* csum_out, void* ws, size_t ws_bytes,
+                   void* stream);
+/* G_out double [d, d] = c^T c.  128 x 128 tiles of the upper triangle times R row ranges; the float32-input MFMA over chains of
+ * scd_pca_chain_rows() rows, float64 across chains and ranges (ascending); G[j][l] and G[l][j] are written from the same sum, so G is
+ * bit-symmetric.  info_out int32 [2] = {rows that hold a non-finite c: G is then not meaningful; 0}.  Two calls return the same bits:
+ * no floating-point atomics, and every partition of the work depends on (n, d) alone. */
+int scd_pca_gram(scd_handle h, const float* X, const float* shift, int64_t n, int d, double* G_out, int32_t* info_out, void* ws,
+                 size_t ws_bytes, void* stream);
+/* Y_out float32 [n, m]: y_ik = sum_j c_ij W_kj, W float32 [m, d] (the components, any whitening scale folded in by the caller), a float32
+ * fma chain from a zero accumulator with j ascending.  unit != 0: each row is divided by its float32 L2 norm over the m columns (sqrtf
+ * and the division correctly rounded); a row of norm 0 is written as zeros.  info_out int32 [2] = {rows with a non-finite y; rows of
+ * norm 0 (unit only)}. */
+int scd_pca_transform(scd_handle h, const float* X, const float* shift, const float* W, int64_t n, int d, int m, int unit, float* Y_out,
+                      int32_t* info_out, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- exact t-SNE: scikit-learn 1.7's TSNE(n_components=2) as the reference's save_tsne / save_tsne_wcolor call it
  *      (local_utils/util.py:178-216), with the exact all-pairs gradient instead of Barnes-Hut's (docs/design/tsne.md) ---- */
 /* The conditional affinities of a k-NN graph: dist2 double [n, k] (squared distances, finite and >= 0), row i ->

@@ -73,9 +73,10 @@ def main(argv=None):
     mask = np.asarray(mask_cls, dtype=bool)[~mask_lab]
 
     cdir = os.path.join(args.root_dir, 'cluster')
-    cpath = os.path.join(cdir, f'{args.cluster}_{mu.feat_cache_name(args)}_{args.dataset_name}.pt')   # :385 (no n_cluster)
+    cpath = os.path.join(cdir, f'{args.cluster}_{mu.feat_cache_name(args)}_{args.dataset_name}{mu.pca_tag(args)}.pt')   # :385 (no n_cluster)
     if args.run_cluster or args.synthetic:
         print(f'Fitting {args.cluster} ...')
+        u_feats, l_feats = mu.pca_reduce(args, u_feats, l_feats)
         all_preds, preds = mu.run_clustering(args, u_feats, l_feats, l_targets, semi_supervised=True)
         if all_preds is None:
             raise SystemExit("--cluster KM gives no labels for the labelled rows (all_preds), which the partially supervised vote "

@@ -92,7 +92,33 @@ def build_parser():
     p.add_argument('--image_list', type=str, default='', help='CSV path,target,labelled of image files for --extract_feat true')
     p.add_argument('--decode', type=str, default='pil', choices=['pil', 'device'],
                    help="--image_list: decode with Pillow on the host, or baseline JPEGs on the device (same pixels; other files through Pillow)")
+    p.add_argument('--pca_dim', type=int, default=0,
+                   help='> 0: the clustering features are reduced to this many principal components (scd_amd.pca.PCA fitted on all rows, '
+                        'labelled and unlabelled) and renormalised to unit rows before the clustering; 0: off')
+    p.add_argument('--pca_whiten', action='store_true', help='--pca_dim: whiten the components (unit variance each) before the renormalisation')
     return p
+
+
+def pca_tag(args):
+    """'' without --pca_dim, else '_pca{M}' ('_pca{M}w' when whitened): the suffix of the names of results computed on reduced features.
+    Read with getattr: callers build their own Namespace."""
+    m = getattr(args, 'pca_dim', 0)
+    return '' if not m else f'_pca{m}' + ('w' if getattr(args, 'pca_whiten', False) else '')
+
+
+def pca_reduce(args, u_feats, l_feats):
+    """--pca_dim M > 0 (docs/design/pca.md): PCA(M, whiten) fitted on ALL rows, labelled first, then each part projected and its rows
+    renormalised to unit length, which every clusterer here expects.  Returns (u_feats, l_feats) as float32 numpy arrays [*, M]; without
+    the flag both come back untouched.  The naming stage and the CLIP similarities keep the original features."""
+    m = getattr(args, 'pca_dim', 0)
+    if not m:
+        return u_feats, l_feats
+    from scd_amd.pca import PCA
+    u, l = np.asarray(u_feats, dtype=np.float32), np.asarray(l_feats, dtype=np.float32).reshape(-1, np.shape(u_feats)[1])
+    pca = PCA(n_components=m, whiten=getattr(args, 'pca_whiten', False)).fit(np.concatenate([l, u]))
+    print(f"PCA: {pca.n_components_} of {u.shape[1]} dimensions keep {pca.explained_variance_ratio_.sum():.4f} of the variance"
+          + (", whitened" if pca.whiten else ""))
+    return tuple(pca.transform(x, unit=True).cpu().numpy() if len(x) else np.zeros((0, pca.n_components_), np.float32) for x in (u, l))
 
 
 def run_gmm(args, u_feats, l_feats=None, l_targets=None):
@@ -163,11 +189,12 @@ def run_hdbscan(args, u_feats):
 
 
 def cluster_result_name(args):
-    """{cluster}_{feat_model}_{dataset}_{n_cluster}.pt; HDBSCAN's result is named by its parameters, the cluster count being a result."""
+    """{cluster}_{feat_model}_{dataset}_{n_cluster}.pt; HDBSCAN's result is named by its parameters, the cluster count being a result;
+    --pca_dim M appends _pca{M} (_pca{M}w when whitened)."""
     tag = str(args.n_cluster)
     if args.cluster == 'HDBSCAN':
         tag = f'mcs{args.min_cluster_size}' + ('' if args.min_samples is None else f'_ms{args.min_samples}')
-    return f'{args.cluster}_{feat_cache_name(args)}_{args.dataset_name}_{tag}.pt'
+    return f'{args.cluster}_{feat_cache_name(args)}_{args.dataset_name}_{tag}{pca_tag(args)}.pt'
 
 
 def load_or_extract(args, model, feat_model_name, out_name):
@@ -316,6 +343,7 @@ def main(argv=None):
     cpath = os.path.join(cdir, cluster_result_name(args))
     if args.run_cluster or args.synthetic:
         print(f'Fitting {args.cluster} ...')
+        u_feats, l_feats = pca_reduce(args, u_feats, l_feats)
         if args.cluster == 'HDBSCAN':
             cluster_result = dict(all_preds=None, u_targets=u_targets, mask=mask, **run_hdbscan(args, u_feats))
         else:

@@ -160,6 +160,15 @@ SIGNATURES = {
     "scd_gmm_em_step": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     # h, X, n, d, k, a, B, C, pred_out, row_ll_out, resp_out, ws, ws_bytes, stream
     "scd_gmm_predict": (_i, [_vp, _vp, _i64, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "scd_pca_ws_bytes": (_sz, [_i64, _i, _i]),
+    "scd_pca_row_tile": (_i, []),
+    "scd_pca_chain_rows": (_i, []),
+    # h, X, shift, n, d, csum_out, ws, ws_bytes, stream
+    "scd_pca_colsum": (_i, [_vp, _vp, _vp, _i64, _i, _vp, _vp, _sz, _vp]),
+    # h, X, shift, n, d, G_out, info_out, ws, ws_bytes, stream
+    "scd_pca_gram": (_i, [_vp, _vp, _vp, _i64, _i, _vp, _vp, _vp, _sz, _vp]),
+    # h, X, shift, W, n, d, m, unit, Y_out, info_out, ws, ws_bytes, stream
+    "scd_pca_transform": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     # h, dist2, n, k, perplexity, p_out, beta_out, info_out, stream
     "scd_tsne_calibrate": (_i, [_vp, _vp, _i64, _i, C.c_double, _vp, _vp, _vp, _vp]),
     "scd_tsne_gradient_ws_bytes": (_sz, [_i64, _i64]),

@@ -1176,6 +1176,64 @@ def gmm_predict(x, a, b, c, want_ll=False, want_resp=False):
     return pred, row_ll, resp
 
 
+# ----------------------------------------------------------------------------- principal components (docs/design/pca.md)
+def _pca_args(who, x, shift):
+    _need_cuda(x, shift)
+    if x.dim() != 2 or x.dtype != torch.float32 or x.shape[0] < 1 or x.shape[1] < 1:
+        raise _lib.ScdError(_lib.SCD_EINVAL, who + ": x float32 [n, d]")
+    if shift is not None:
+        if shift.dtype != torch.float32 or shift.shape != (x.shape[1],):
+            raise _lib.ScdError(_lib.SCD_EINVAL, who + ": shift float32 [d] or None")
+        shift = shift.contiguous()
+    return x.contiguous(), shift
+
+
+def _pca_ws(who, n, d, m, device):
+    nb = _L().scd_pca_ws_bytes(n, d, m)
+    if nb == 0:
+        raise _lib.ScdError(_lib.SCD_EINVAL, "%s: outside the limits 1 <= n < 2^31, 1 <= d <= 1024, 1 <= m <= 1024 (n = %d, d = %d, m = %d)"
+                            % (who, n, d, m))
+    return _ws(nb, device), nb
+
+
+def pca_colsum(x, shift=None):
+    """scd_pca_colsum: x float32 [n, d], shift float32 [d] or None -> csum float64 [d] = sum_i fl32(x_ij - shift_j), on the device."""
+    x, shift = _pca_args("pca_colsum", x, shift)
+    n, d = x.shape
+    csum = torch.empty(d, dtype=torch.float64, device=x.device)
+    ws, nb = _pca_ws("pca_colsum", n, d, 1, x.device)
+    check(_L().scd_pca_colsum(handle(), ptr(x), ptr(shift), n, d, ptr(csum), ptr(ws), nb, stream_ptr()))
+    return csum
+
+
+def pca_gram(x, shift=None):
+    """scd_pca_gram: x float32 [n, d], shift float32 [d] or None -> (G float64 [d, d] = c^T c with c = fl32(x - shift), bit-symmetric;
+    info int32 [2] = rows that hold a non-finite value, 0), on the device."""
+    x, shift = _pca_args("pca_gram", x, shift)
+    n, d = x.shape
+    g = torch.empty((d, d), dtype=torch.float64, device=x.device)
+    info = torch.empty(2, dtype=torch.int32, device=x.device)
+    ws, nb = _pca_ws("pca_gram", n, d, 1, x.device)
+    check(_L().scd_pca_gram(handle(), ptr(x), ptr(shift), n, d, ptr(g), ptr(info), ptr(ws), nb, stream_ptr()))
+    return g, info
+
+
+def pca_transform(x, w, shift=None, unit=False):
+    """scd_pca_transform: x float32 [n, d], w float32 [m, d], shift float32 [d] or None -> (y float32 [n, m] = fl32(x - shift) w^T, with
+    unit each row divided by its float32 L2 norm (a row of norm 0 is zeros); info int32 [2] = rows with a non-finite y, rows of norm 0)."""
+    x, shift = _pca_args("pca_transform", x, shift)
+    _need_cuda(w)
+    n, d = x.shape
+    if w.dim() != 2 or w.dtype != torch.float32 or w.shape[1] != d or w.shape[0] < 1:
+        raise _lib.ScdError(_lib.SCD_EINVAL, "pca_transform: w float32 [m, d]")
+    w, m = w.contiguous(), w.shape[0]
+    y = torch.empty((n, m), dtype=torch.float32, device=x.device)
+    info = torch.empty(2, dtype=torch.int32, device=x.device)
+    ws, nb = _pca_ws("pca_transform", 1, d, m, x.device)
+    check(_L().scd_pca_transform(handle(), ptr(x), ptr(shift), ptr(w), n, d, m, int(bool(unit)), ptr(y), ptr(info), ptr(ws), nb, stream_ptr()))
+    return y, info
+
+
 # ----------------------------------------------------------------------------- host solvers
 def munkres(cost):
     """linear_assignment (cluster_utils.py:234): int array [n,m] -> sorted pairs [min(n,m),2]."""
