@@ -30,6 +30,7 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-ato
 # probe.hip: the plain FLAGS - expf, logf and the division are the correctly rounded-to-2-ulp library forms its error model charges
 # gmm.hip: the plain FLAGS, for probe.hip's reason (its error model charges the same library forms)
 # pca.hip: the plain FLAGS, for probe.hip's reason (sqrtf and the division of its unit rows are the correctly rounded forms)
+# f32mm.h, which those three share, states the contract in its header comment: include it only from units built with the plain FLAGS
 # tsne.hip: no contraction - its fused multiply-adds are written out, and its update step must be the IEEE operations numpy performs
 # graph.hip: no contraction - the sparse product's row sums are a multiply and an add per term, the order its contract states
 EXTRA = {"sim.hip": ["-fno-slp-vectorize"], "image.hip": ["-ffp-contract=off", "-fno-fast-math"], "tsne.hip": ["-ffp-contract=off"], "graph.hip": ["-ffp-contract=off"]}

@@ -1,6 +1,7 @@
 // Gaussian mixtures with diagonal covariances on gfx950: one EM step of scikit-learn's GaussianMixture(covariance_type='diag' |
 // 'spherical') with labelled rows clamped to their class (the semi-supervised mixture of GPC), and the forward pass alone.
 // docs/design/gmm.md has the semantics, the error model and the resources.
+// The tile shapes, the k-octet packing, the float64 range sums and the host's range plan are f32mm.h's, shared with probe.hip and pca.hip.
 //
 //   scd_gmm_em_step   z_ik = a_k + sum_d x_id B_kd + sum_d x_id^2 C_kd (the weighted log-density; the caller forms a, B = mu / v and
 //                     C = -1 / (2 v) in float64 and rounds them to float32), r_ik = s_i softmax_k(z_i) on an unlabelled row and
@@ -11,7 +12,7 @@
 //                          way.  Lane half h of the MFMA reads its four k values of a stream with one 16-byte load, and the two
 //                          streams of an octet share one 64-byte segment: a wave's 32 components touch 32 segments per octet, where
 //                          two slabs would touch 64 half-used ones a slab apart;
-//                       2. gmm_fwd_kernel: a block owns GM_RT = 32 rows and all kp components, wave w the 32-component tiles w, w + 4,
+//                       2. gmm_fwd_kernel: a block owns F32MM_RT = 32 rows and all kp components, wave w the 32-component tiles w, w + 4,
 //                          ... in up to 8 accumulator tiles of v_mfma_f32_32x32x2_f32.  X goes through LDS once, in chunks of 64 k;
 //                          each staged x feeds two MFMAs, x against B and x * x (one float32 multiply in a register) against C.
 //                          The accumulator starts at zero; octets of k ascend; within an octet the eight x B products come first (k
@@ -20,7 +21,7 @@
 //                          r = s (e / sum) or the one-hot of the label -> r [n, kp] fp32 (padding columns 0), the row's
 //                          log-likelihood in float64 -> [n], argmax = the lowest component that attains the maximum;
 //                       3. gmm_moment_kernel: 128 x 128 tiles of (component, dim) times R row ranges times the two moments
-//                          (blockIdx.z = 1 squares x as it is staged); the float32 MFMA runs over chains of at most GM_CHAIN = 256
+//                          (blockIdx.z = 1 squares x as it is staged); the float32 MFMA runs over chains of at most F32MM_CHAIN = 256
 //                          rows, each chain's tile is added into float64 registers -> part [2, R, k, d].  gmm_nk_kernel: float64
 //                          column sums of r and float64 sums of the row log-likelihoods over RB row ranges;
 //                       4. gmm_finish_kernel: the ranges' partials added in ascending order -> ll, nk, s1, s2 (float64).
@@ -30,54 +31,33 @@
 //
 // No floating-point atomics (the two info counters are integers).  R, RB and every tile depend on (n, d, k) alone: two calls return the
 // same bits on any device.
-#include "common.h"
-
-#define GM_RT 32                                // rows of a forward block
-#define GM_BK 64                                // k of an X chunk in LDS
-#define GM_XLD 65                               // its row stride in floats
-#define GM_THREADS 256
-#define GM_DMAX 1024
-#define GM_KMAX 1024
-#define GM_CHAIN 256                            // rows of a float32 accumulation chain in the moments
-#define GM_GT 128                               // moment tile: components and dims
-#define GM_GK 32                                // rows of r and X per LDS stage
-#define GM_GLD 160                              // LDS row stride in floats: the two lane halves (rows k, k + 1) read distinct banks
-#define GM_NK_ROWS 2048                         // rows per range of the column-sum kernel, at most GM_NK_RANGES ranges
-#define GM_NK_RANGES 64
-
-// row of the 32 x 32 MFMA result a lane holds in accumulator register reg (lane half h); its column is lane & 31
-__device__ __forceinline__ int gm_row(int reg, int h) { return (reg & 3) + 8 * (reg >> 2) + 4 * h; }
+#include "f32mm.h"
 
 // ------------------------------------------------------------------------------------------------ 1. pack B and C
 __global__ void __launch_bounds__(256) gmm_pack_kernel(const float* __restrict__ B, const float* __restrict__ Cq, int k, int d, int kp, int dp,
                                                        float* __restrict__ BCp) {
-    const int e = blockIdx.x * 256 + threadIdx.x;
-    if (e >= kp * 2 * dp) return;
-    const int comp = e / (2 * dp), q = e % (2 * dp);
-    const int w = q & 15, pos = w & 7;
-    const int dim = (q >> 4) * 8 + 2 * (pos & 3) + (pos >> 2);
-    const float* src = (w >> 3) ? Cq : B;
-    BCp[e] = (comp < k && dim < d) ? src[(size_t)comp * d + dim] : 0.f;
+    const float* const src[2] = {B, Cq};
+    f32mm_pack<2>(src, k, d, kp, dp, BCp);
 }
 
 // ------------------------------------------------------------------------------------------------ 2. logits, softmax, responsibilities
 // PREDICT = false: r [n, kp] (the clamped responsibilities times the weight), rowll double [n].
 // PREDICT = true:  resp [n, k] dense (the softmax), rowlse float [n]; y, sw are not read.
 template <int NT, bool PREDICT>
-__global__ void __launch_bounds__(GM_THREADS) gmm_fwd_kernel(const float* __restrict__ X, const int* __restrict__ y, const float* __restrict__ sw,
+__global__ void __launch_bounds__(F32MM_THREADS) gmm_fwd_kernel(const float* __restrict__ X, const int* __restrict__ y, const float* __restrict__ sw,
                                                              long long n, int d, int dp, int k, int kp, const float* __restrict__ BCp,
                                                              const float* __restrict__ a, float* __restrict__ r, double* __restrict__ rowll,
                                                              float* __restrict__ rowlse, int* __restrict__ pred, int* __restrict__ info) {
-    __shared__ float xs[GM_RT * GM_XLD];
-    __shared__ float red_a[4][GM_RT];           // per wave: row maximum
-    __shared__ float red_b[4][GM_RT];           // per wave: row sum of e
-    __shared__ int red_i[4][GM_RT];             // per wave: lowest component at the maximum
-    __shared__ float zy_s[GM_RT], s_s[GM_RT];
-    __shared__ int y_s[GM_RT], bad_s[GM_RT];
-    const long long row0 = (long long)blockIdx.x * GM_RT;
+    __shared__ float xs[F32MM_RT * F32MM_XLD];
+    __shared__ float red_a[4][F32MM_RT];        // per wave: row maximum
+    __shared__ float red_b[4][F32MM_RT];        // per wave: row sum of e
+    __shared__ int red_i[4][F32MM_RT];          // per wave: lowest component at the maximum
+    __shared__ float zy_s[F32MM_RT], s_s[F32MM_RT];
+    __shared__ int y_s[F32MM_RT], bad_s[F32MM_RT];
+    const long long row0 = (long long)blockIdx.x * F32MM_RT;
     const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63, li = lane & 31, h = lane >> 5;
 
-    if (tid < GM_RT) {
+    if (tid < F32MM_RT) {
         const long long g = row0 + tid;
         int yy = -1;
         float s = 0.f;
@@ -107,12 +87,12 @@ __global__ void __launch_bounds__(GM_THREADS) gmm_fwd_kernel(const float* __rest
 
     // no branch around a load: the chunk after the current one is in registers while the MFMAs run (addresses clamped, values masked);
     // the operand after the current one (C of this octet, then B of the next) is in registers as well
-    float xr[GM_RT * GM_BK / GM_THREADS];
+    float xr[F32MM_RT * F32MM_BK / F32MM_THREADS];
     f32x4 cur[NT], nx[NT];
     auto load_x = [&](int k0) {
 #pragma unroll
-        for (int i = 0; i < GM_RT * GM_BK / GM_THREADS; ++i) {
-            const int idx = tid + GM_THREADS * i, row = idx >> 6, kk = k0 + (idx & 63);
+        for (int i = 0; i < F32MM_RT * F32MM_BK / F32MM_THREADS; ++i) {
+            const int idx = tid + F32MM_THREADS * i, row = idx >> 6, kk = k0 + (idx & 63);
             const long long g = row0 + row < n ? row0 + row : n - 1;
             xr[i] = X[(size_t)g * d + (kk < d ? kk : d - 1)];
         }
@@ -120,22 +100,22 @@ __global__ void __launch_bounds__(GM_THREADS) gmm_fwd_kernel(const float* __rest
     load_x(0);
 #pragma unroll
     for (int t = 0; t < NT; ++t) cur[t] = *reinterpret_cast<const f32x4*>(BCp + woff[t]);
-    for (int k0 = 0; k0 < dp; k0 += GM_BK) {
+    for (int k0 = 0; k0 < dp; k0 += F32MM_BK) {
         __syncthreads();
 #pragma unroll
-        for (int i = 0; i < GM_RT * GM_BK / GM_THREADS; ++i) {
-            const int idx = tid + GM_THREADS * i, row = idx >> 6, kk = idx & 63;
-            xs[row * GM_XLD + kk] = (row0 + row < n && k0 + kk < d) ? xr[i] : 0.f;
+        for (int i = 0; i < F32MM_RT * F32MM_BK / F32MM_THREADS; ++i) {
+            const int idx = tid + F32MM_THREADS * i, row = idx >> 6, kk = idx & 63;
+            xs[row * F32MM_XLD + kk] = (row0 + row < n && k0 + kk < d) ? xr[i] : 0.f;
         }
         __syncthreads();
-        load_x(k0 + GM_BK);
-        const int kend = dp - k0 < GM_BK ? dp - k0 : GM_BK;     // a multiple of 8
+        load_x(k0 + F32MM_BK);
+        const int kend = dp - k0 < F32MM_BK ? dp - k0 : F32MM_BK;               // a multiple of 8
         for (int k8 = 0; k8 < kend; k8 += 8) {
             const int oct = 2 * (k0 + k8);                      // floats from the row's start to this octet's B
             const int onext = k0 + k8 + 8 < dp ? oct + 16 : oct;
             float xv[4];
 #pragma unroll
-            for (int j = 0; j < 4; ++j) xv[j] = xs[li * GM_XLD + k8 + 2 * j + h];
+            for (int j = 0; j < 4; ++j) xv[j] = xs[li * F32MM_XLD + k8 + 2 * j + h];
             // x against B
 #pragma unroll
             for (int t = 0; t < NT; ++t) nx[t] = *reinterpret_cast<const f32x4*>(BCp + woff[t] + oct + 8);
@@ -159,7 +139,7 @@ __global__ void __launch_bounds__(GM_THREADS) gmm_fwd_kernel(const float* __rest
         }
     }
 
-    // acc[t][q] = z of row gm_row(q, h), component (4 t + wave) * 32 + li, without a
+    // acc[t][q] = z of row f32mm_row(q, h), component (4 t + wave) * 32 + li, without a
     float m[16];
 #pragma unroll
     for (int q = 0; q < 16; ++q) m[q] = -INFINITY;
@@ -182,7 +162,7 @@ __global__ void __launch_bounds__(GM_THREADS) gmm_fwd_kernel(const float* __rest
     if (bad) {
 #pragma unroll
         for (int q = 0; q < 16; ++q)
-            if (bad & (1 << q)) atomicOr(&bad_s[gm_row(q, h)], 1);
+            if (bad & (1 << q)) atomicOr(&bad_s[f32mm_row(q, h)], 1);
     }
 #pragma unroll
     for (int o = 16; o > 0; o >>= 1)
@@ -190,12 +170,12 @@ __global__ void __launch_bounds__(GM_THREADS) gmm_fwd_kernel(const float* __rest
         for (int q = 0; q < 16; ++q) m[q] = fmaxf(m[q], __shfl_xor(m[q], o, 64));
     if (li == 0) {
 #pragma unroll
-        for (int q = 0; q < 16; ++q) red_a[wave][gm_row(q, h)] = m[q];
+        for (int q = 0; q < 16; ++q) red_a[wave][f32mm_row(q, h)] = m[q];
     }
     __syncthreads();
 #pragma unroll
     for (int q = 0; q < 16; ++q) {
-        const int row = gm_row(q, h);
+        const int row = f32mm_row(q, h);
         float v = red_a[0][row];
 #pragma unroll
         for (int w = 1; w < 4; ++w) v = fmaxf(v, red_a[w][row]);
@@ -209,8 +189,8 @@ __global__ void __launch_bounds__(GM_THREADS) gmm_fwd_kernel(const float* __rest
     for (int q = 0; q < 16; ++q) {
         sum[q] = 0.f;
         cand[q] = 0x7fffffff;
-        yv[q] = y_s[gm_row(q, h)];
-        sv[q] = s_s[gm_row(q, h)];
+        yv[q] = y_s[f32mm_row(q, h)];
+        sv[q] = s_s[f32mm_row(q, h)];
     }
 #pragma unroll
     for (int t = NT - 1; t >= 0; --t) {                         // descending: the lowest component is kept last
@@ -220,7 +200,7 @@ __global__ void __launch_bounds__(GM_THREADS) gmm_fwd_kernel(const float* __rest
         for (int q = 0; q < 16; ++q) {
             const float z = acc[t][q];
             if (valid && z == m[q]) cand[q] = comp;
-            if (!PREDICT && valid && comp == yv[q]) zy_s[gm_row(q, h)] = z;
+            if (!PREDICT && valid && comp == yv[q]) zy_s[f32mm_row(q, h)] = z;
             const float ev = valid ? expf(z - m[q]) : 0.f;
             acc[t][q] = ev;
             sum[q] += ev;
@@ -237,8 +217,8 @@ __global__ void __launch_bounds__(GM_THREADS) gmm_fwd_kernel(const float* __rest
     if (li == 0) {
 #pragma unroll
         for (int q = 0; q < 16; ++q) {
-            red_i[wave][gm_row(q, h)] = cand[q];
-            red_b[wave][gm_row(q, h)] = sum[q];
+            red_i[wave][f32mm_row(q, h)] = cand[q];
+            red_b[wave][f32mm_row(q, h)] = sum[q];
         }
     }
     __syncthreads();
@@ -246,7 +226,7 @@ __global__ void __launch_bounds__(GM_THREADS) gmm_fwd_kernel(const float* __rest
     if (r) {
 #pragma unroll
         for (int q = 0; q < 16; ++q) {
-            const int row = gm_row(q, h);
+            const int row = f32mm_row(q, h);
             sum[q] = ((red_b[0][row] + red_b[1][row]) + red_b[2][row]) + red_b[3][row];
         }
 #pragma unroll
@@ -255,7 +235,7 @@ __global__ void __launch_bounds__(GM_THREADS) gmm_fwd_kernel(const float* __rest
             const bool valid = comp < k;
 #pragma unroll
             for (int q = 0; q < 16; ++q) {
-                const long long g = row0 + gm_row(q, h);
+                const long long g = row0 + f32mm_row(q, h);
                 const float p = acc[t][q] / sum[q];
                 if (PREDICT) {
                     if (g < n && valid) r[(size_t)g * k + comp] = p;
@@ -266,7 +246,7 @@ __global__ void __launch_bounds__(GM_THREADS) gmm_fwd_kernel(const float* __rest
             }
         }
     }
-    if (tid < GM_RT) {
+    if (tid < F32MM_RT) {
         const long long g = row0 + tid;
         if (g < n) {
             float mx = red_a[0][tid];
@@ -304,14 +284,14 @@ __global__ void __launch_bounds__(256) gmm_hard_kernel(const int* __restrict__ y
 // ------------------------------------------------------------------------------------------------ 3. moment partials, nk and ll partials
 // grid (component tiles * dim tiles, R, 2).  part [2, R, k, d] float64: z = 0 is r^T X, z = 1 is r^T (X o X), x squared in float32 as it
 // is staged.
-__global__ void __launch_bounds__(GM_THREADS) gmm_moment_kernel(const float* __restrict__ r, const float* __restrict__ X, long long n, int d, int k,
+__global__ void __launch_bounds__(F32MM_THREADS) gmm_moment_kernel(const float* __restrict__ r, const float* __restrict__ X, long long n, int d, int k,
                                                                 int kp, int ctiles, long long rows_per_range, double* __restrict__ part) {
-    __shared__ float rs[GM_GK * GM_GLD];
-    __shared__ float xs[GM_GK * GM_GLD];
-    const int c0 = (blockIdx.x % ctiles) * GM_GT, d0 = (blockIdx.x / ctiles) * GM_GT;
+    __shared__ float rs[F32MM_GK * F32MM_GLD];
+    __shared__ float xs[F32MM_GK * F32MM_GLD];
+    const int c0 = (blockIdx.x % ctiles) * F32MM_GT, d0 = (blockIdx.x / ctiles) * F32MM_GT;
     const bool sq = blockIdx.z != 0;
-    const long long lo = (long long)blockIdx.y * rows_per_range;
-    const long long hi = lo + rows_per_range < n ? lo + rows_per_range : n;
+    long long lo, hi;
+    f32mm_range(rows_per_range, n, lo, hi);
     const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63, li = lane & 31, h = lane >> 5;
     const int wm = wave >> 1, wn = wave & 1;
     bool on[2][2];
@@ -333,37 +313,37 @@ __global__ void __launch_bounds__(GM_THREADS) gmm_moment_kernel(const float* __r
             }
 
     // no branch around a load: the next 32 rows are in registers while the MFMAs run (addresses clamped, values masked)
-    float rr[GM_GK * GM_GT / GM_THREADS], xr[GM_GK * GM_GT / GM_THREADS];
+    float rr[F32MM_GK * F32MM_GT / F32MM_THREADS], xr[F32MM_GK * F32MM_GT / F32MM_THREADS];
     auto load_rows = [&](long long base) {
 #pragma unroll
-        for (int i = 0; i < GM_GK * GM_GT / GM_THREADS; ++i) {
-            const int idx = tid + GM_THREADS * i, row = idx >> 7, col = idx & 127;
+        for (int i = 0; i < F32MM_GK * F32MM_GT / F32MM_THREADS; ++i) {
+            const int idx = tid + F32MM_THREADS * i, row = idx >> 7, col = idx & 127;
             const long long g = base + row < hi ? base + row : hi - 1;
             rr[i] = r[(size_t)g * kp + (c0 + col < kp ? c0 + col : kp - 1)];
             xr[i] = X[(size_t)g * d + (d0 + col < d ? d0 + col : d - 1)];
         }
     };
     load_rows(lo);
-    for (long long base = lo; base < hi; base += GM_GK) {
+    for (long long base = lo; base < hi; base += F32MM_GK) {
         __syncthreads();
 #pragma unroll
-        for (int i = 0; i < GM_GK * GM_GT / GM_THREADS; ++i) {
-            const int idx = tid + GM_THREADS * i, row = idx >> 7, col = idx & 127;
+        for (int i = 0; i < F32MM_GK * F32MM_GT / F32MM_THREADS; ++i) {
+            const int idx = tid + F32MM_THREADS * i, row = idx >> 7, col = idx & 127;
             const bool in = base + row < hi;
             const float xv = sq ? xr[i] * xr[i] : xr[i];
-            rs[row * GM_GLD + col] = (in && c0 + col < kp) ? rr[i] : 0.f;
-            xs[row * GM_GLD + col] = (in && d0 + col < d) ? xv : 0.f;
+            rs[row * F32MM_GLD + col] = (in && c0 + col < kp) ? rr[i] : 0.f;
+            xs[row * F32MM_GLD + col] = (in && d0 + col < d) ? xv : 0.f;
         }
         __syncthreads();
-        load_rows(base + GM_GK);
+        load_rows(base + F32MM_GK);
 #pragma unroll 4
-        for (int s = 0; s < GM_GK / 2; ++s) {
+        for (int s = 0; s < F32MM_GK / 2; ++s) {
             const int kk = 2 * s + h;
             float av[2], bv[2];
 #pragma unroll
             for (int i = 0; i < 2; ++i) {
-                av[i] = rs[kk * GM_GLD + wm * 64 + i * 32 + li];
-                bv[i] = xs[kk * GM_GLD + wn * 64 + i * 32 + li];
+                av[i] = rs[kk * F32MM_GLD + wm * 64 + i * 32 + li];
+                bv[i] = xs[kk * F32MM_GLD + wn * 64 + i * 32 + li];
             }
 #pragma unroll
             for (int i = 0; i < 2; ++i)
@@ -371,7 +351,7 @@ __global__ void __launch_bounds__(GM_THREADS) gmm_moment_kernel(const float* __r
                 for (int j = 0; j < 2; ++j)
                     if (on[i][j]) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[i], bv[j], acc[i][j], 0, 0, 0);
         }
-        if ((base - lo + GM_GK) % GM_CHAIN == 0 || base + GM_GK >= hi) {        // the end of a chain: into float64
+        if ((base - lo + F32MM_GK) % F32MM_CHAIN == 0 || base + F32MM_GK >= hi) {  // the end of a chain: into float64
 #pragma unroll
             for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -390,41 +370,24 @@ __global__ void __launch_bounds__(GM_THREADS) gmm_moment_kernel(const float* __r
         for (int j = 0; j < 2; ++j)
 #pragma unroll
             for (int q = 0; q < 16; ++q) {
-                const int comp = c0 + wm * 64 + i * 32 + gm_row(q, h), dim = d0 + wn * 64 + j * 32 + li;
+                const int comp = c0 + wm * 64 + i * 32 + f32mm_row(q, h), dim = d0 + wn * 64 + j * 32 + li;
                 if (comp < k && dim < d) out[(size_t)comp * d + dim] = acc64[i][j][q];
             }
 }
 
 // grid (kp / 32, RB): float64 column sums of r over a row range -> nkpart [RB, kp]; the blocks of column group 0 also sum the range's
 // row log-likelihoods -> llpart [RB]
-__global__ void __launch_bounds__(GM_THREADS) gmm_nk_kernel(const float* __restrict__ r, const double* __restrict__ rowll, long long n, int kp,
-                                                            long long rows_per_range, double* __restrict__ nkpart, double* __restrict__ llpart) {
-    __shared__ double sh[GM_THREADS];
-    const long long lo = (long long)blockIdx.y * rows_per_range;
-    const long long hi = lo + rows_per_range < n ? lo + rows_per_range : n;
-    const int tid = threadIdx.x, cl = tid & 31, rsub = tid >> 5;
-    const int comp = blockIdx.x * 32 + cl;
-    double a = 0.0;
-    for (long long g = lo + rsub; g < hi; g += 8) a += (double)r[(size_t)g * kp + comp];
-    sh[tid] = a;
-    __syncthreads();
-    if (tid < 32) {
-        double t = sh[tid];
-#pragma unroll
-        for (int q = 1; q < 8; ++q) t += sh[tid + 32 * q];
-        nkpart[(size_t)blockIdx.y * kp + comp] = t;
-    }
+__global__ void __launch_bounds__(F32MM_THREADS) gmm_nk_kernel(const float* __restrict__ r, const double* __restrict__ rowll, long long n, int kp,
+                                                               long long rows_per_range, double* __restrict__ nkpart, double* __restrict__ llpart) {
+    __shared__ double sh[F32MM_THREADS];
+    long long lo, hi;
+    f32mm_range(rows_per_range, n, lo, hi);
+    const int tid = threadIdx.x, comp = blockIdx.x * 32 + (tid & 31);
+    const double t = f32mm_colsum(lo, hi, [&](long long g) { return r[(size_t)g * kp + comp]; }, sh);
+    if (tid < 32) nkpart[(size_t)blockIdx.y * kp + comp] = t;
     if (blockIdx.x != 0) return;
-    __syncthreads();
-    a = 0.0;
-    for (long long g = lo + tid; g < hi; g += GM_THREADS) a += rowll[g];
-    sh[tid] = a;
-    __syncthreads();
-    for (int o = GM_THREADS / 2; o > 0; o >>= 1) {
-        if (tid < o) sh[tid] += sh[tid + o];
-        __syncthreads();
-    }
-    if (tid == 0) llpart[blockIdx.y] = sh[0];
+    const double l = f32mm_rowsum(rowll, lo, hi, sh);
+    if (tid == 0) llpart[blockIdx.y] = l;
 }
 
 // ------------------------------------------------------------------------------------------------ 4. the ranges in ascending order
@@ -435,20 +398,15 @@ __global__ void __launch_bounds__(256) gmm_finish_kernel(const double* __restric
     const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
     const long long kd = (long long)k * d;
     if (e < 2 * kd) {
-        const double* src = part + (e < kd ? 0 : (size_t)R * kd);
-        const long long el = e < kd ? e : e - kd;
-        double a = 0.0;
-        for (int q = 0; q < R; ++q) a += src[(size_t)q * kd + el];
-        (e < kd ? s1 : s2)[el] = a;
+        const bool first = e < kd;
+        const long long el = first ? e : e - kd;
+        double* dst = first ? s1 : s2;
+        dst[el] = f32mm_range_sum(first ? part : part + (size_t)R * kd, kd, el, R);
     } else if (e < 2 * kd + k) {
         const int comp = (int)(e - 2 * kd);
-        double a = 0.0;
-        for (int q = 0; q < RB; ++q) a += nkpart[(size_t)q * kp + comp];
-        nk[comp] = a;
+        nk[comp] = f32mm_range_sum(nkpart, kp, comp, RB);
     } else if (e == 2 * kd + k) {
-        double a = 0.0;
-        for (int q = 0; q < RB; ++q) a += llpart[q];
-        ll[0] = a;
+        ll[0] = f32mm_range_sum(llpart, 1, 0, RB);
     }
 }
 
@@ -458,26 +416,13 @@ struct gmm_plan {
     size_t bcp, r, rowll, part, nkpart, llpart, end;
 };
 
-static bool gmm_shape_ok(int64_t n, int d, int k) { return n >= 1 && n < (1ll << 31) && d >= 1 && d <= GM_DMAX && k >= 1 && k <= GM_KMAX; }
-
 static void gmm_layout(int64_t n, int d, int k, gmm_plan& p) {
-    p.kp = (int)scd_cdiv(k, 32) * 32;
-    p.dp = (int)scd_cdiv(d, 8) * 8;
-    p.ctiles = (int)scd_cdiv(p.kp, GM_GT);
-    p.dtiles = (int)scd_cdiv(d, GM_GT);
-    // row ranges of the moments: at least four chains each, at most 32, about 1024 blocks over the two moments; a whole number of
-    // chains per range
-    const long long chains = scd_cdiv(n, GM_CHAIN);
-    long long R = chains / 4, cap = scd_cdiv(512, (long long)p.ctiles * p.dtiles);
-    if (cap > 32) cap = 32;
-    if (R > cap) R = cap;
-    if (R < 1) R = 1;
-    p.rows_per_range = scd_cdiv(chains, R) * GM_CHAIN;
-    p.R = (int)scd_cdiv(n, p.rows_per_range);
-    long long RB = scd_cdiv(n, GM_NK_ROWS);
-    if (RB > GM_NK_RANGES) RB = GM_NK_RANGES;
-    p.nk_rows = scd_cdiv(n, RB);
-    p.RB = (int)scd_cdiv(n, p.nk_rows);
+    p.kp = f32mm_pad(k, 32);
+    p.dp = f32mm_pad(d, 8);
+    p.ctiles = (int)scd_cdiv(p.kp, F32MM_GT);
+    p.dtiles = (int)scd_cdiv(d, F32MM_GT);
+    f32mm_ranges(n, (long long)p.ctiles * p.dtiles, 512, p.R, p.rows_per_range);    // 512: about 1024 blocks over the two moments
+    f32mm_colsum_ranges(n, p.RB, p.nk_rows);
     p.bcp = 0;                                                                      // BCp    f32 [kp, 2 dp]
     p.r = p.bcp + scd_align((size_t)p.kp * 2 * p.dp * 4);                           // r      f32 [n, kp]
     p.rowll = p.r + scd_align((size_t)n * p.kp * 4);                                // rowll  f64 [n]
@@ -487,32 +432,20 @@ static void gmm_layout(int64_t n, int d, int k, gmm_plan& p) {
     p.end = p.llpart + scd_align((size_t)p.RB * 8);
 }
 
-extern "C" int scd_gmm_row_tile(void) { return GM_RT; }
-extern "C" int scd_gmm_chain_rows(void) { return GM_CHAIN; }
+extern "C" int scd_gmm_row_tile(void) { return F32MM_RT; }
+extern "C" int scd_gmm_chain_rows(void) { return F32MM_CHAIN; }
 
 extern "C" size_t scd_gmm_ws_bytes(int64_t n, int d, int k) {
-    if (!gmm_shape_ok(n, d, k)) return 0;
+    if (!f32mm_shape_ok(n, d, k, 1)) return 0;
     gmm_plan p;
     gmm_layout(n, d, k, p);
     return p.end;
 }
 
-#define GMM_SHAPE_REQUIRE(who)                                                                                    \
-    SCD_REQUIRE(n >= 1 && n < (1ll << 31), who ": n = %lld outside [1, 2^31)", (long long)n);                     \
-    SCD_REQUIRE(d >= 1 && d <= GM_DMAX, who ": d = %d outside [1, %d]", d, GM_DMAX);                              \
-    SCD_REQUIRE(k >= 1 && k <= GM_KMAX, who ": k = %d outside [1, %d]", k, GM_KMAX);                              \
-    SCD_REQUIRE((uintptr_t)ws % 16 == 0, who ": workspace not 16-byte aligned")
-
-// the forward kernel with NT = the component tiles of a wave: kp / 32 tiles over four waves, rounded up to 1, 2, 4 or 8
-#define GMM_FWD(PRED, ...)                                                                                        \
-    do {                                                                                                          \
-        const int per_ = (int)scd_cdiv(p.kp / 32, 4);                                                             \
-        const unsigned grid_ = (unsigned)scd_cdiv(n, GM_RT);                                                      \
-        if (per_ <= 1) gmm_fwd_kernel<1, PRED><<<grid_, GM_THREADS, 0, st>>>(__VA_ARGS__);                        \
-        else if (per_ <= 2) gmm_fwd_kernel<2, PRED><<<grid_, GM_THREADS, 0, st>>>(__VA_ARGS__);                   \
-        else if (per_ <= 4) gmm_fwd_kernel<4, PRED><<<grid_, GM_THREADS, 0, st>>>(__VA_ARGS__);                   \
-        else gmm_fwd_kernel<8, PRED><<<grid_, GM_THREADS, 0, st>>>(__VA_ARGS__);                                  \
-    } while (0)
+#define GMM_SHAPE_REQUIRE(who)              \
+    F32MM_ND_REQUIRE(who, n, d);            \
+    F32MM_WIDTH_REQUIRE(who, "k", k, 1);    \
+    F32MM_WS_REQUIRE(who, ws)
 
 extern "C" int scd_gmm_em_step(scd_handle h, const float* X, const int32_t* y, const float* sample_weight, int64_t n, int d, int k,
                                const float* a, const float* B, const float* C, double* ll_out, double* nk_out, double* s1_out,
@@ -541,11 +474,14 @@ extern "C" int scd_gmm_em_step(scd_handle h, const float* X, const int32_t* y, c
         gmm_hard_kernel<<<(unsigned)n, 256, 0, st>>>(y, sample_weight, k, p.kp, r, info_out);
     } else {
         gmm_pack_kernel<<<(unsigned)scd_cdiv((int64_t)p.kp * 2 * p.dp, 256), 256, 0, st>>>(B, C, k, d, p.kp, p.dp, BCp);
-        GMM_FWD(false, X, y, sample_weight, n, d, p.dp, k, p.kp, BCp, a, r, rowll, nullptr, pred_out, info_out);
+        f32mm_fwd_dispatch(n, p.kp, [&](unsigned grid, auto nt) {
+            gmm_fwd_kernel<decltype(nt)::value, false><<<grid, F32MM_THREADS, 0, st>>>(X, y, sample_weight, n, d, p.dp, k, p.kp, BCp, a, r, rowll,
+                                                                                       nullptr, pred_out, info_out);
+        });
     }
-    gmm_moment_kernel<<<dim3((unsigned)(p.ctiles * p.dtiles), (unsigned)p.R, 2), GM_THREADS, 0, st>>>(r, X, n, d, k, p.kp, p.ctiles,
-                                                                                                     p.rows_per_range, part);
-    gmm_nk_kernel<<<dim3((unsigned)(p.kp / 32), (unsigned)p.RB), GM_THREADS, 0, st>>>(r, rowll, n, p.kp, p.nk_rows, nkpart, llpart);
+    gmm_moment_kernel<<<dim3((unsigned)(p.ctiles * p.dtiles), (unsigned)p.R, 2), F32MM_THREADS, 0, st>>>(r, X, n, d, k, p.kp, p.ctiles,
+                                                                                                        p.rows_per_range, part);
+    gmm_nk_kernel<<<dim3((unsigned)(p.kp / 32), (unsigned)p.RB), F32MM_THREADS, 0, st>>>(r, rowll, n, p.kp, p.nk_rows, nkpart, llpart);
     gmm_finish_kernel<<<(unsigned)scd_cdiv((int64_t)2 * k * d + k + 1, 256), 256, 0, st>>>(part, nkpart, llpart, k, d, p.kp, p.R, p.RB, s1_out,
                                                                                           s2_out, nk_out, ll_out);
     SCD_LAUNCH_CHECK();
@@ -565,7 +501,10 @@ extern "C" int scd_gmm_predict(scd_handle h, const float* X, int64_t n, int d, i
     int* info = (int*)((char*)ws + p.r);                        // the two counters of the forward kernel: not reported
     SCD_HIP(hipMemsetAsync(info, 0, 8, st));
     gmm_pack_kernel<<<(unsigned)scd_cdiv((int64_t)p.kp * 2 * p.dp, 256), 256, 0, st>>>(B, C, k, d, p.kp, p.dp, BCp);
-    GMM_FWD(true, X, nullptr, nullptr, n, d, p.dp, k, p.kp, BCp, a, resp_out, nullptr, row_ll_out, pred_out, info);
+    f32mm_fwd_dispatch(n, p.kp, [&](unsigned grid, auto nt) {
+        gmm_fwd_kernel<decltype(nt)::value, true><<<grid, F32MM_THREADS, 0, st>>>(X, nullptr, nullptr, n, d, p.dp, k, p.kp, BCp, a, resp_out, nullptr,
+                                                                                  row_ll_out, pred_out, info);
+    });
     SCD_LAUNCH_CHECK();
     return SCD_OK;
 }

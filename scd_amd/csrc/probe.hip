@@ -1,13 +1,14 @@
 // The linear probe's evaluation on gfx950: the data term of multinomial logistic regression on frozen features and its gradient
 // (the linear evaluation of DINO / DINOv2, scikit-learn's LogisticRegression(C) as a sum).  docs/design/probe.md has the semantics, the
 // error model and the resources.
+// The tile shapes, the k-octet packing, the float64 range sums and the host's range plan are f32mm.h's, shared with gmm.hip and pca.hip.
 //
 //   scd_probe_loss_grad   loss = sum_i s_i [lse_c(z_ic) - z_{i,y_i}],  gW = r^T X,  gb = column sums of r,  z_ic = W_c . x_i + b_c,
 //                         r_ic = s_i (softmax(z_i)_c - [c == y_i]), in four steps:
 //                           1. probe_pack_kernel: W [c, d] -> Wp [cp, dp] (cp = c up to 32, dp = d up to 8, zero filled), the 8 values of
 //                              a k-octet stored as k+0, k+2, k+4, k+6, k+1, k+3, k+5, k+7: lane half h of the MFMA reads its four k
 //                              values (k + 2 j + h) of an octet with one 16-byte load;
-//                           2. probe_fwd_kernel: a block owns PB_RT = 32 rows and all cp classes, wave w the 32-class tiles w, w + 4, ...
+//                           2. probe_fwd_kernel: a block owns F32MM_RT = 32 rows and all cp classes, wave w the 32-class tiles w, w + 4, ...
 //                              in up to 8 accumulator tiles of v_mfma_f32_32x32x2_f32 (128 accumulator registers at c = 1024).  X goes through LDS in
 //                              chunks of 64 k, Wp streams from L2.  The sum over k ascends from a zero accumulator (the MFMA is a
 //                              k-ordered fmaf chain), b_c is added last.  The softmax stays in registers: row maximum over the real
@@ -16,7 +17,7 @@
 //                              attains the maximum.  The 32 lanes of a half reduce with shuffles, the four waves through LDS in wave
 //                              order;
 //                           3. probe_grad_kernel: 128 x 128 tiles of (class, dim) times R row ranges; r and X rows go through LDS 32 at
-//                              a time, the float32 MFMA runs over chains of at most PB_CHAIN = 256 rows, each chain's tile is added
+//                              a time, the float32 MFMA runs over chains of at most F32MM_CHAIN = 256 rows, each chain's tile is added
 //                              into float64 registers; a range's float64 tile -> part [R, c, d].  probe_gb_kernel: float64 column sums
 //                              of r and float64 sums of the row losses over RB row ranges;
 //                           4. probe_finish_kernel: the ranges' partials added in ascending order -> loss, gW, gb (float64).
@@ -24,49 +25,30 @@
 //
 // No floating-point atomics (the two info counters are integers).  R, RB and every tile depend on (n, d, c) alone: two calls return the
 // same bits on any device.
-#include "common.h"
-
-#define PB_RT 32                                // rows of a forward block
-#define PB_BK 64                                // k of an X chunk in LDS
-#define PB_XLD 65                               // its row stride in floats
-#define PB_THREADS 256
-#define PB_DMAX 1024
-#define PB_CMAX 1024
-#define PB_CHAIN 256                            // rows of a float32 accumulation chain in the gradient
-#define PB_GT 128                               // gradient tile: classes and dims
-#define PB_GK 32                                // rows of r and X per LDS stage
-#define PB_GLD 160                              // LDS row stride in floats: the two lane halves (rows k, k + 1) read distinct banks
-#define PB_GB_ROWS 2048                         // rows per range of the column-sum kernel, at most PB_GB_RANGES ranges
-#define PB_GB_RANGES 64
-
-// row of the 32 x 32 MFMA result a lane holds in accumulator register reg (lane half h); its column is lane & 31
-__device__ __forceinline__ int pb_row(int reg, int h) { return (reg & 3) + 8 * (reg >> 2) + 4 * h; }
+#include "f32mm.h"
 
 // ------------------------------------------------------------------------------------------------ 1. pack W
 __global__ void __launch_bounds__(256) probe_pack_kernel(const float* __restrict__ W, int c, int d, int cp, int dp, float* __restrict__ Wp) {
-    const int e = blockIdx.x * 256 + threadIdx.x;
-    if (e >= cp * dp) return;
-    const int cls = e / dp, q = e % dp;
-    const int k = (q & ~7) + 2 * (q & 3) + ((q & 7) >> 2);
-    Wp[e] = (cls < c && k < d) ? W[(size_t)cls * d + k] : 0.f;
+    const float* const src[1] = {W};
+    f32mm_pack<1>(src, c, d, cp, dp, Wp);
 }
 
 // ------------------------------------------------------------------------------------------------ 2. logits and softmax residual
 template <int NT, bool PREDICT>
-__global__ void __launch_bounds__(PB_THREADS) probe_fwd_kernel(const float* __restrict__ X, const int* __restrict__ y, const float* __restrict__ sw,
+__global__ void __launch_bounds__(F32MM_THREADS) probe_fwd_kernel(const float* __restrict__ X, const int* __restrict__ y, const float* __restrict__ sw,
                                                                long long n, int d, int dp, int c, int cp, const float* __restrict__ Wp,
                                                                const float* __restrict__ b, float* __restrict__ r, float* __restrict__ rowloss,
                                                                int* __restrict__ pred, float* __restrict__ top2, int* __restrict__ info) {
-    __shared__ float xs[PB_RT * PB_XLD];
-    __shared__ float red_a[4][PB_RT];           // per wave: row maximum (PREDICT: largest logit)
-    __shared__ float red_b[4][PB_RT];           // per wave: row sum of e (PREDICT: second largest logit)
-    __shared__ int red_i[4][PB_RT];             // per wave: lowest class at the maximum
-    __shared__ float zy_s[PB_RT], s_s[PB_RT];
-    __shared__ int y_s[PB_RT], bad_s[PB_RT];
-    const long long row0 = (long long)blockIdx.x * PB_RT;
+    __shared__ float xs[F32MM_RT * F32MM_XLD];
+    __shared__ float red_a[4][F32MM_RT];        // per wave: row maximum (PREDICT: largest logit)
+    __shared__ float red_b[4][F32MM_RT];        // per wave: row sum of e (PREDICT: second largest logit)
+    __shared__ int red_i[4][F32MM_RT];          // per wave: lowest class at the maximum
+    __shared__ float zy_s[F32MM_RT], s_s[F32MM_RT];
+    __shared__ int y_s[F32MM_RT], bad_s[F32MM_RT];
+    const long long row0 = (long long)blockIdx.x * F32MM_RT;
     const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63, li = lane & 31, h = lane >> 5;
 
-    if (tid < PB_RT) {
+    if (tid < F32MM_RT) {
         const long long g = row0 + tid;
         int yy = -1;
         float s = 0.f;
@@ -96,12 +78,12 @@ __global__ void __launch_bounds__(PB_THREADS) probe_fwd_kernel(const float* __re
     }
 
     // no branch around a load: the chunk after the current one is in registers while the MFMAs run (addresses clamped, values masked)
-    float xr[PB_RT * PB_BK / PB_THREADS];
+    float xr[F32MM_RT * F32MM_BK / F32MM_THREADS];
     f32x4 bw[NT], bn[NT];
     auto load_x = [&](int k0) {
 #pragma unroll
-        for (int i = 0; i < PB_RT * PB_BK / PB_THREADS; ++i) {
-            const int idx = tid + PB_THREADS * i, row = idx >> 6, k = k0 + (idx & 63);
+        for (int i = 0; i < F32MM_RT * F32MM_BK / F32MM_THREADS; ++i) {
+            const int idx = tid + F32MM_THREADS * i, row = idx >> 6, k = k0 + (idx & 63);
             const long long g = row0 + row < n ? row0 + row : n - 1;
             xr[i] = X[(size_t)g * d + (k < d ? k : d - 1)];
         }
@@ -109,23 +91,23 @@ __global__ void __launch_bounds__(PB_THREADS) probe_fwd_kernel(const float* __re
     load_x(0);
 #pragma unroll
     for (int t = 0; t < NT; ++t) bw[t] = *reinterpret_cast<const f32x4*>(Wp + woff[t]);
-    for (int k0 = 0; k0 < dp; k0 += PB_BK) {
+    for (int k0 = 0; k0 < dp; k0 += F32MM_BK) {
         __syncthreads();
 #pragma unroll
-        for (int i = 0; i < PB_RT * PB_BK / PB_THREADS; ++i) {
-            const int idx = tid + PB_THREADS * i, row = idx >> 6, kk = idx & 63;
-            xs[row * PB_XLD + kk] = (row0 + row < n && k0 + kk < d) ? xr[i] : 0.f;
+        for (int i = 0; i < F32MM_RT * F32MM_BK / F32MM_THREADS; ++i) {
+            const int idx = tid + F32MM_THREADS * i, row = idx >> 6, kk = idx & 63;
+            xs[row * F32MM_XLD + kk] = (row0 + row < n && k0 + kk < d) ? xr[i] : 0.f;
         }
         __syncthreads();
-        load_x(k0 + PB_BK);
-        const int kend = dp - k0 < PB_BK ? dp - k0 : PB_BK;     // a multiple of 8
+        load_x(k0 + F32MM_BK);
+        const int kend = dp - k0 < F32MM_BK ? dp - k0 : F32MM_BK;               // a multiple of 8
         for (int k8 = 0; k8 < kend; k8 += 8) {
             const int kn = k0 + k8 + 8 < dp ? k0 + k8 + 8 : dp - 8;
 #pragma unroll
             for (int t = 0; t < NT; ++t) bn[t] = *reinterpret_cast<const f32x4*>(Wp + woff[t] + kn);
             float a[4];
 #pragma unroll
-            for (int j = 0; j < 4; ++j) a[j] = xs[li * PB_XLD + k8 + 2 * j + h];
+            for (int j = 0; j < 4; ++j) a[j] = xs[li * F32MM_XLD + k8 + 2 * j + h];
 #pragma unroll
             for (int j = 0; j < 4; ++j)
 #pragma unroll
@@ -135,7 +117,7 @@ __global__ void __launch_bounds__(PB_THREADS) probe_fwd_kernel(const float* __re
         }
     }
 
-    // acc[t][q] = z of row pb_row(q, h), class (4 t + wave) * 32 + li, without b
+    // acc[t][q] = z of row f32mm_row(q, h), class (4 t + wave) * 32 + li, without b
     float m[16], m2[16];
 #pragma unroll
     for (int q = 0; q < 16; ++q) m[q] = m2[q] = -INFINITY;
@@ -169,7 +151,7 @@ __global__ void __launch_bounds__(PB_THREADS) probe_fwd_kernel(const float* __re
     if (bad) {
 #pragma unroll
         for (int q = 0; q < 16; ++q)
-            if (bad & (1 << q)) atomicOr(&bad_s[pb_row(q, h)], 1);
+            if (bad & (1 << q)) atomicOr(&bad_s[f32mm_row(q, h)], 1);
     }
 #pragma unroll
     for (int o = 16; o > 0; o >>= 1)
@@ -185,14 +167,14 @@ __global__ void __launch_bounds__(PB_THREADS) probe_fwd_kernel(const float* __re
     if (li == 0) {
 #pragma unroll
         for (int q = 0; q < 16; ++q) {
-            red_a[wave][pb_row(q, h)] = m[q];
-            if (PREDICT) red_b[wave][pb_row(q, h)] = m2[q];
+            red_a[wave][f32mm_row(q, h)] = m[q];
+            if (PREDICT) red_b[wave][f32mm_row(q, h)] = m2[q];
         }
     }
     __syncthreads();
 #pragma unroll
     for (int q = 0; q < 16; ++q) {
-        const int row = pb_row(q, h);
+        const int row = f32mm_row(q, h);
         float v = red_a[0][row];
 #pragma unroll
         for (int w = 1; w < 4; ++w) v = fmaxf(v, red_a[w][row]);
@@ -206,8 +188,8 @@ __global__ void __launch_bounds__(PB_THREADS) probe_fwd_kernel(const float* __re
     for (int q = 0; q < 16; ++q) {
         sum[q] = 0.f;
         cand[q] = 0x7fffffff;
-        yv[q] = y_s[pb_row(q, h)];
-        sv[q] = s_s[pb_row(q, h)];
+        yv[q] = y_s[f32mm_row(q, h)];
+        sv[q] = s_s[f32mm_row(q, h)];
     }
 #pragma unroll
     for (int t = NT - 1; t >= 0; --t) {                         // descending: the lowest class is kept last
@@ -219,7 +201,7 @@ __global__ void __launch_bounds__(PB_THREADS) probe_fwd_kernel(const float* __re
                 const float z = acc[t][q];
                 if (valid && z == m[q]) cand[q] = cls;
                 if (!PREDICT) {
-                    if (valid && cls == yv[q]) zy_s[pb_row(q, h)] = z;
+                    if (valid && cls == yv[q]) zy_s[f32mm_row(q, h)] = z;
                     const float ev = valid ? expf(z - m[q]) : 0.f;
                     acc[t][q] = ev;
                     sum[q] += ev;
@@ -238,8 +220,8 @@ __global__ void __launch_bounds__(PB_THREADS) probe_fwd_kernel(const float* __re
     if (li == 0) {
 #pragma unroll
         for (int q = 0; q < 16; ++q) {
-            red_i[wave][pb_row(q, h)] = cand[q];
-            if (!PREDICT) red_b[wave][pb_row(q, h)] = sum[q];
+            red_i[wave][f32mm_row(q, h)] = cand[q];
+            if (!PREDICT) red_b[wave][f32mm_row(q, h)] = sum[q];
         }
     }
     __syncthreads();
@@ -247,7 +229,7 @@ __global__ void __launch_bounds__(PB_THREADS) probe_fwd_kernel(const float* __re
     if (!PREDICT) {
 #pragma unroll
         for (int q = 0; q < 16; ++q) {
-            const int row = pb_row(q, h);
+            const int row = f32mm_row(q, h);
             sum[q] = ((red_b[0][row] + red_b[1][row]) + red_b[2][row]) + red_b[3][row];
         }
 #pragma unroll
@@ -257,7 +239,7 @@ __global__ void __launch_bounds__(PB_THREADS) probe_fwd_kernel(const float* __re
                 const bool valid = cls < c;
 #pragma unroll
                 for (int q = 0; q < 16; ++q) {
-                    const int row = pb_row(q, h);
+                    const int row = f32mm_row(q, h);
                     const long long g = row0 + row;
                     if (g < n && cls < cp) {
                         const float p = acc[t][q] / sum[q];
@@ -267,7 +249,7 @@ __global__ void __launch_bounds__(PB_THREADS) probe_fwd_kernel(const float* __re
             }
         }
     }
-    if (tid < PB_RT) {
+    if (tid < F32MM_RT) {
         const long long g = row0 + tid;
         if (g < n) {
             float mx = red_a[0][tid];
@@ -304,13 +286,13 @@ __global__ void __launch_bounds__(PB_THREADS) probe_fwd_kernel(const float* __re
 
 // ------------------------------------------------------------------------------------------------ 3. gW partials, gb and loss partials
 // grid (class tiles * dim tiles, R).  part [R, c, d] float64.
-__global__ void __launch_bounds__(PB_THREADS) probe_grad_kernel(const float* __restrict__ r, const float* __restrict__ X, long long n, int d, int c,
+__global__ void __launch_bounds__(F32MM_THREADS) probe_grad_kernel(const float* __restrict__ r, const float* __restrict__ X, long long n, int d, int c,
                                                                 int cp, int ctiles, long long rows_per_range, double* __restrict__ part) {
-    __shared__ float rs[PB_GK * PB_GLD];
-    __shared__ float xs[PB_GK * PB_GLD];
-    const int c0 = (blockIdx.x % ctiles) * PB_GT, d0 = (blockIdx.x / ctiles) * PB_GT;
-    const long long lo = (long long)blockIdx.y * rows_per_range;
-    const long long hi = lo + rows_per_range < n ? lo + rows_per_range : n;
+    __shared__ float rs[F32MM_GK * F32MM_GLD];
+    __shared__ float xs[F32MM_GK * F32MM_GLD];
+    const int c0 = (blockIdx.x % ctiles) * F32MM_GT, d0 = (blockIdx.x / ctiles) * F32MM_GT;
+    long long lo, hi;
+    f32mm_range(rows_per_range, n, lo, hi);
     const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63, li = lane & 31, h = lane >> 5;
     const int wm = wave >> 1, wn = wave & 1;
     bool on[2][2];
@@ -332,36 +314,36 @@ __global__ void __launch_bounds__(PB_THREADS) probe_grad_kernel(const float* __r
             }
 
     // no branch around a load: the next 32 rows are in registers while the MFMAs run (addresses clamped, values masked)
-    float rr[PB_GK * PB_GT / PB_THREADS], xr[PB_GK * PB_GT / PB_THREADS];
+    float rr[F32MM_GK * F32MM_GT / F32MM_THREADS], xr[F32MM_GK * F32MM_GT / F32MM_THREADS];
     auto load_rows = [&](long long base) {
 #pragma unroll
-        for (int i = 0; i < PB_GK * PB_GT / PB_THREADS; ++i) {
-            const int idx = tid + PB_THREADS * i, row = idx >> 7, col = idx & 127;
+        for (int i = 0; i < F32MM_GK * F32MM_GT / F32MM_THREADS; ++i) {
+            const int idx = tid + F32MM_THREADS * i, row = idx >> 7, col = idx & 127;
             const long long g = base + row < hi ? base + row : hi - 1;
             rr[i] = r[(size_t)g * cp + (c0 + col < cp ? c0 + col : cp - 1)];
             xr[i] = X[(size_t)g * d + (d0 + col < d ? d0 + col : d - 1)];
         }
     };
     load_rows(lo);
-    for (long long base = lo; base < hi; base += PB_GK) {
+    for (long long base = lo; base < hi; base += F32MM_GK) {
         __syncthreads();
 #pragma unroll
-        for (int i = 0; i < PB_GK * PB_GT / PB_THREADS; ++i) {
-            const int idx = tid + PB_THREADS * i, row = idx >> 7, col = idx & 127;
+        for (int i = 0; i < F32MM_GK * F32MM_GT / F32MM_THREADS; ++i) {
+            const int idx = tid + F32MM_THREADS * i, row = idx >> 7, col = idx & 127;
             const bool in = base + row < hi;
-            rs[row * PB_GLD + col] = (in && c0 + col < cp) ? rr[i] : 0.f;
-            xs[row * PB_GLD + col] = (in && d0 + col < d) ? xr[i] : 0.f;
+            rs[row * F32MM_GLD + col] = (in && c0 + col < cp) ? rr[i] : 0.f;
+            xs[row * F32MM_GLD + col] = (in && d0 + col < d) ? xr[i] : 0.f;
         }
         __syncthreads();
-        load_rows(base + PB_GK);
+        load_rows(base + F32MM_GK);
 #pragma unroll 4
-        for (int s = 0; s < PB_GK / 2; ++s) {
+        for (int s = 0; s < F32MM_GK / 2; ++s) {
             const int k = 2 * s + h;
             float a[2], bv[2];
 #pragma unroll
             for (int i = 0; i < 2; ++i) {
-                a[i] = rs[k * PB_GLD + wm * 64 + i * 32 + li];
-                bv[i] = xs[k * PB_GLD + wn * 64 + i * 32 + li];
+                a[i] = rs[k * F32MM_GLD + wm * 64 + i * 32 + li];
+                bv[i] = xs[k * F32MM_GLD + wn * 64 + i * 32 + li];
             }
 #pragma unroll
             for (int i = 0; i < 2; ++i)
@@ -369,7 +351,7 @@ __global__ void __launch_bounds__(PB_THREADS) probe_grad_kernel(const float* __r
                 for (int j = 0; j < 2; ++j)
                     if (on[i][j]) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i], bv[j], acc[i][j], 0, 0, 0);
         }
-        if ((base - lo + PB_GK) % PB_CHAIN == 0 || base + PB_GK >= hi) {        // the end of a chain: into float64
+        if ((base - lo + F32MM_GK) % F32MM_CHAIN == 0 || base + F32MM_GK >= hi) {  // the end of a chain: into float64
 #pragma unroll
             for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -387,42 +369,25 @@ __global__ void __launch_bounds__(PB_THREADS) probe_grad_kernel(const float* __r
         for (int j = 0; j < 2; ++j)
 #pragma unroll
             for (int q = 0; q < 16; ++q) {
-                const int cls = c0 + wm * 64 + i * 32 + pb_row(q, h), dim = d0 + wn * 64 + j * 32 + li;
+                const int cls = c0 + wm * 64 + i * 32 + f32mm_row(q, h), dim = d0 + wn * 64 + j * 32 + li;
                 if (cls < c && dim < d) part[((size_t)blockIdx.y * c + cls) * d + dim] = acc64[i][j][q];
             }
 }
 
 // grid (cp / 32, RB): float64 column sums of r over a row range -> gbpart [RB, cp]; the blocks of column group 0 also sum the range's
 // row losses -> losspart [RB]
-__global__ void __launch_bounds__(PB_THREADS) probe_gb_kernel(const float* __restrict__ r, const float* __restrict__ rowloss, long long n, int cp,
-                                                              long long rows_per_range, double* __restrict__ gbpart,
-                                                              double* __restrict__ losspart) {
-    __shared__ double sh[PB_THREADS];
-    const long long lo = (long long)blockIdx.y * rows_per_range;
-    const long long hi = lo + rows_per_range < n ? lo + rows_per_range : n;
-    const int tid = threadIdx.x, cl = tid & 31, rsub = tid >> 5;
-    const int cls = blockIdx.x * 32 + cl;
-    double a = 0.0;
-    for (long long g = lo + rsub; g < hi; g += 8) a += (double)r[(size_t)g * cp + cls];
-    sh[tid] = a;
-    __syncthreads();
-    if (tid < 32) {
-        double t = sh[tid];
-#pragma unroll
-        for (int q = 1; q < 8; ++q) t += sh[tid + 32 * q];
-        gbpart[(size_t)blockIdx.y * cp + cls] = t;
-    }
+__global__ void __launch_bounds__(F32MM_THREADS) probe_gb_kernel(const float* __restrict__ r, const float* __restrict__ rowloss, long long n, int cp,
+                                                                 long long rows_per_range, double* __restrict__ gbpart,
+                                                                 double* __restrict__ losspart) {
+    __shared__ double sh[F32MM_THREADS];
+    long long lo, hi;
+    f32mm_range(rows_per_range, n, lo, hi);
+    const int tid = threadIdx.x, cls = blockIdx.x * 32 + (tid & 31);
+    const double t = f32mm_colsum(lo, hi, [&](long long g) { return r[(size_t)g * cp + cls]; }, sh);
+    if (tid < 32) gbpart[(size_t)blockIdx.y * cp + cls] = t;
     if (blockIdx.x != 0) return;
-    __syncthreads();
-    a = 0.0;
-    for (long long g = lo + tid; g < hi; g += PB_THREADS) a += (double)rowloss[g];
-    sh[tid] = a;
-    __syncthreads();
-    for (int o = PB_THREADS / 2; o > 0; o >>= 1) {
-        if (tid < o) sh[tid] += sh[tid + o];
-        __syncthreads();
-    }
-    if (tid == 0) losspart[blockIdx.y] = sh[0];
+    const double l = f32mm_rowsum(rowloss, lo, hi, sh);
+    if (tid == 0) losspart[blockIdx.y] = l;
 }
 
 // ------------------------------------------------------------------------------------------------ 4. the ranges in ascending order
@@ -432,20 +397,12 @@ __global__ void __launch_bounds__(256) probe_finish_kernel(const double* __restr
     const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
     const long long cd = (long long)c * d;
     if (e < cd) {
-        double a = 0.0;
-        for (int q = 0; q < R; ++q) a += part[(size_t)q * cd + e];
-        gW[e] = a;
+        gW[e] = f32mm_range_sum(part, cd, e, R);
     } else if (e < cd + c) {
-        if (gb) {
-            const int cls = (int)(e - cd);
-            double a = 0.0;
-            for (int q = 0; q < RB; ++q) a += gbpart[(size_t)q * cp + cls];
-            gb[cls] = a;
-        }
+        const int cls = (int)(e - cd);
+        if (gb) gb[cls] = f32mm_range_sum(gbpart, cp, cls, RB);
     } else if (e == cd + c) {
-        double a = 0.0;
-        for (int q = 0; q < RB; ++q) a += losspart[q];
-        loss[0] = a;
+        loss[0] = f32mm_range_sum(losspart, 1, 0, RB);
     }
 }
 
@@ -455,25 +412,13 @@ struct probe_plan {
     size_t wp, r, rowloss, part, gbpart, losspart, end;
 };
 
-static bool probe_shape_ok(int64_t n, int d, int c) { return n >= 1 && n < (1ll << 31) && d >= 1 && d <= PB_DMAX && c >= 2 && c <= PB_CMAX; }
-
 static void probe_layout(int64_t n, int d, int c, probe_plan& p) {
-    p.cp = (int)scd_cdiv(c, 32) * 32;
-    p.dp = (int)scd_cdiv(d, 8) * 8;
-    p.ctiles = (int)scd_cdiv(p.cp, PB_GT);
-    p.dtiles = (int)scd_cdiv(d, PB_GT);
-    // row ranges of the gradient: at least four chains each, at most 32, about 1024 blocks; a whole number of chains per range
-    const long long chains = scd_cdiv(n, PB_CHAIN);
-    long long R = chains / 4, cap = scd_cdiv(1024, (long long)p.ctiles * p.dtiles);
-    if (cap > 32) cap = 32;
-    if (R > cap) R = cap;
-    if (R < 1) R = 1;
-    p.rows_per_range = scd_cdiv(chains, R) * PB_CHAIN;
-    p.R = (int)scd_cdiv(n, p.rows_per_range);
-    long long RB = scd_cdiv(n, PB_GB_ROWS);
-    if (RB > PB_GB_RANGES) RB = PB_GB_RANGES;
-    p.gb_rows = scd_cdiv(n, RB);
-    p.RB = (int)scd_cdiv(n, p.gb_rows);
+    p.cp = f32mm_pad(c, 32);
+    p.dp = f32mm_pad(d, 8);
+    p.ctiles = (int)scd_cdiv(p.cp, F32MM_GT);
+    p.dtiles = (int)scd_cdiv(d, F32MM_GT);
+    f32mm_ranges(n, (long long)p.ctiles * p.dtiles, 1024, p.R, p.rows_per_range);
+    f32mm_colsum_ranges(n, p.RB, p.gb_rows);
     p.wp = 0;                                                                       // Wp       f32 [cp, dp]
     p.r = p.wp + scd_align((size_t)p.cp * p.dp * 4);                                // r        f32 [n, cp]
     p.rowloss = p.r + scd_align((size_t)n * p.cp * 4);                              // rowloss  f32 [n]
@@ -483,32 +428,20 @@ static void probe_layout(int64_t n, int d, int c, probe_plan& p) {
     p.end = p.losspart + scd_align((size_t)p.RB * 8);
 }
 
-extern "C" int scd_probe_row_tile(void) { return PB_RT; }
-extern "C" int scd_probe_chain_rows(void) { return PB_CHAIN; }
+extern "C" int scd_probe_row_tile(void) { return F32MM_RT; }
+extern "C" int scd_probe_chain_rows(void) { return F32MM_CHAIN; }
 
 extern "C" size_t scd_probe_ws_bytes(int64_t n, int d, int c) {
-    if (!probe_shape_ok(n, d, c)) return 0;
+    if (!f32mm_shape_ok(n, d, c, 2)) return 0;
     probe_plan p;
     probe_layout(n, d, c, p);
     return p.end;
 }
 
-#define PROBE_SHAPE_REQUIRE(who)                                                                                  \
-    SCD_REQUIRE(n >= 1 && n < (1ll << 31), who ": n = %lld outside [1, 2^31)", (long long)n);                     \
-    SCD_REQUIRE(d >= 1 && d <= PB_DMAX, who ": d = %d outside [1, %d]", d, PB_DMAX);                              \
-    SCD_REQUIRE(c >= 2 && c <= PB_CMAX, who ": c = %d outside [2, %d]", c, PB_CMAX);                              \
-    SCD_REQUIRE((uintptr_t)ws % 16 == 0, who ": workspace not 16-byte aligned")
-
-// the forward kernel with NT = the class tiles of a wave: cp / 32 tiles over four waves, rounded up to 1, 2, 4 or 8
-#define PROBE_FWD(PRED, ...)                                                                                      \
-    do {                                                                                                          \
-        const int per_ = (int)scd_cdiv(p.cp / 32, 4);                                                             \
-        const unsigned grid_ = (unsigned)scd_cdiv(n, PB_RT);                                                      \
-        if (per_ <= 1) probe_fwd_kernel<1, PRED><<<grid_, PB_THREADS, 0, st>>>(__VA_ARGS__);                      \
-        else if (per_ <= 2) probe_fwd_kernel<2, PRED><<<grid_, PB_THREADS, 0, st>>>(__VA_ARGS__);                 \
-        else if (per_ <= 4) probe_fwd_kernel<4, PRED><<<grid_, PB_THREADS, 0, st>>>(__VA_ARGS__);                 \
-        else probe_fwd_kernel<8, PRED><<<grid_, PB_THREADS, 0, st>>>(__VA_ARGS__);                                \
-    } while (0)
+#define PROBE_SHAPE_REQUIRE(who)            \
+    F32MM_ND_REQUIRE(who, n, d);            \
+    F32MM_WIDTH_REQUIRE(who, "c", c, 2);    \
+    F32MM_WS_REQUIRE(who, ws)
 
 extern "C" int scd_probe_loss_grad(scd_handle h, const float* X, const int32_t* y, const float* sample_weight, int64_t n, int d, int c,
                                    const float* W, const float* b, double* loss_out, double* gW_out, double* gb_out, int32_t* pred_out,
@@ -530,10 +463,13 @@ extern "C" int scd_probe_loss_grad(scd_handle h, const float* X, const int32_t* 
 
     SCD_HIP(hipMemsetAsync(info_out, 0, 8, st));
     probe_pack_kernel<<<(unsigned)scd_cdiv((int64_t)p.cp * p.dp, 256), 256, 0, st>>>(W, c, d, p.cp, p.dp, Wp);
-    PROBE_FWD(false, X, y, sample_weight, n, d, p.dp, c, p.cp, Wp, b, r, rowloss, pred_out, nullptr, info_out);
-    probe_grad_kernel<<<dim3((unsigned)(p.ctiles * p.dtiles), (unsigned)p.R), PB_THREADS, 0, st>>>(r, X, n, d, c, p.cp, p.ctiles, p.rows_per_range,
-                                                                                                  part);
-    probe_gb_kernel<<<dim3((unsigned)(p.cp / 32), (unsigned)p.RB), PB_THREADS, 0, st>>>(r, rowloss, n, p.cp, p.gb_rows, gbpart, losspart);
+    f32mm_fwd_dispatch(n, p.cp, [&](unsigned grid, auto nt) {
+        probe_fwd_kernel<decltype(nt)::value, false><<<grid, F32MM_THREADS, 0, st>>>(X, y, sample_weight, n, d, p.dp, c, p.cp, Wp, b, r, rowloss,
+                                                                                     pred_out, nullptr, info_out);
+    });
+    probe_grad_kernel<<<dim3((unsigned)(p.ctiles * p.dtiles), (unsigned)p.R), F32MM_THREADS, 0, st>>>(r, X, n, d, c, p.cp, p.ctiles,
+                                                                                                     p.rows_per_range, part);
+    probe_gb_kernel<<<dim3((unsigned)(p.cp / 32), (unsigned)p.RB), F32MM_THREADS, 0, st>>>(r, rowloss, n, p.cp, p.gb_rows, gbpart, losspart);
     probe_finish_kernel<<<(unsigned)scd_cdiv((int64_t)c * d + c + 1, 256), 256, 0, st>>>(part, gbpart, losspart, c, d, p.cp, p.R, p.RB, gW_out,
                                                                                          gb_out, loss_out);
     SCD_LAUNCH_CHECK();
@@ -553,7 +489,10 @@ extern "C" int scd_probe_predict(scd_handle h, const float* X, int64_t n, int d,
     int* info = (int*)((char*)ws + p.r);                        // the two counters of the forward kernel: not reported
     SCD_HIP(hipMemsetAsync(info, 0, 8, st));
     probe_pack_kernel<<<(unsigned)scd_cdiv((int64_t)p.cp * p.dp, 256), 256, 0, st>>>(W, c, d, p.cp, p.dp, Wp);
-    PROBE_FWD(true, X, nullptr, nullptr, n, d, p.dp, c, p.cp, Wp, b, nullptr, nullptr, pred_out, top_logit_out, info);
+    f32mm_fwd_dispatch(n, p.cp, [&](unsigned grid, auto nt) {
+        probe_fwd_kernel<decltype(nt)::value, true><<<grid, F32MM_THREADS, 0, st>>>(X, nullptr, nullptr, n, d, p.dp, c, p.cp, Wp, b, nullptr, nullptr,
+                                                                                    pred_out, top_logit_out, info);
+    });
     SCD_LAUNCH_CHECK();
     return SCD_OK;
 }
