@@ -13,6 +13,7 @@ All features, labelled and unlabelled, are L2-normalised once (estimate_k.py:61)
   --criterion bic             label-free: a diagonal Gaussian mixture of K components (scd_amd.gmm, --covariance_type) is fitted
                               instead of k-means and the K with the LOWEST Bayesian information criterion wins; integer grid search
                               by default.  One n x K x d pass per EM step and no n x n pass; K <= 1024, d <= 1024.
+                              --covariance_type full | tied fits scd_amd.gmm_full's mixture instead: d <= 64, so with --pca_dim.
 
 Fits and scores run on the GPU (scd_amd.cluster.KMeans, scd_amd.metrics).  Writes
 ROOT/cluster/estimated_k_{feat_model}_{dataset_name}.json and prints the value to pass as --n_cluster.
@@ -47,7 +48,8 @@ def build_parser():
     p.add_argument('--criterion', type=str, default='acc', choices=['acc', 'silhouette', 'bic'],
                    help='acc: clustering accuracy on the labelled rows (GCD); silhouette: mean silhouette coefficient, needs no labels; '
                         'bic: lowest Bayesian information criterion of a diagonal Gaussian mixture, needs no labels')
-    p.add_argument('--covariance_type', type=str, default='diag', choices=['diag', 'spherical'], help="--criterion bic: the mixture's covariances")
+    p.add_argument('--covariance_type', type=str, default='diag', choices=['diag', 'spherical', 'full', 'tied'],
+                   help="--criterion bic: the mixture's covariances; full and tied (scd_amd.gmm_full) take rows of at most 64 dimensions")
     p.add_argument('--search_mode', type=str, default=None, choices=['brent', 'binary', 'grid', 'finch'],
                    help='Mode for black box optimisation; default: brent for acc, grid for silhouette and bic.  finch: score only the '
                         'cluster counts of FINCH\'s partitions of all rows, clipped to [min_classes, max_classes]')

@@ -549,6 +549,43 @@ int scd_gmm_em_step(scd_handle h, const float* X, const int32_t* y, const float*
 int scd_gmm_predict(scd_handle h, const float* X, int64_t n, int d, int k, const float* a, const float* B, const float* C,
                     int32_t* pred_out, float* row_ll_out, float* resp_out, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- Gaussian mixtures with a full covariance matrix per component, on rows of at most 64 dimensions (what scd_pca_transform gives):
+ *      scikit-learn 1.7's GaussianMixture(covariance_type='full'; 'tied' is the same call with one factor replicated k times), labelled
+ *      rows clamped as in scd_gmm_em_step (docs/design/gmm_full.md) ---- */
+/* Bytes of workspace of scd_gmm_full_em_step for X [n, d] and k components: the packed Ut and mu, the responsibilities r float32 [n, k
+ * up to 32], the row log-likelihoods float64 [n] and the float64 partial sums of the row ranges (32 MB a range for S at k = 1000,
+ * d = 64); 0.69 GB at n = 126,976, d = 64, k = 1000.  0 outside the limits 1 <= n < 2^31, 1 <= d <= 64, 1 <= k <= 1024.
+ * scd_gmm_full_predict needs scd_gmm_full_ws_bytes(1, d, k) whatever its n. */
+size_t scd_gmm_full_ws_bytes(int64_t n, int d, int k);
+/* Rows of X a block of the forward kernel owns (with all k components). */
+int scd_gmm_full_row_tile(void);
+/* The longest float32 accumulation chain over rows in S (<= 1024): a chain's 32 x 32 tile is added into float64. */
+int scd_gmm_full_chain_rows(void);
+/* One E-step and the sufficient statistics of the M-step, taken about the current means, at the weighted log-densities
+ *   c_ikl = fl32(x_il - mu_kl),   y_ikj = sum_l c_ikl U_k[l][j],   q_ik = sum_j y_ikj^2,   z_ik = a_k - 0.5 q_ik,
+ *   a_k = log w_k + sum_j log U_k[j][j]      (the constant -(d / 2) log 2 pi is the caller's to add to ll)
+ * with U_k scikit-learn's precisions_cholesky_ (upper triangular, U_k U_k^T = Sigma_k^-1).  The caller forms a, mu and U in float64 and
+ * rounds them to float32.  X float32 [n, d]; y int32 [n] or NULL; a float32 [k]; mu float32 [k, d]; Ut float32 [k, d, d] with
+ * Ut[k][j][l] = U_k[l][j], its entries with l > j exact zeros (the kernel skips those beyond a 32-column tile; a zero product adds an
+ * exact zero, so the bits do not depend on that); s_i = sample_weight[i], or 1 when it is NULL.
+ * Rows, labels, y_i >= k (info[0]), non-finite logits (info[1]), the softmax (maximum over the real components, expf, a correctly
+ * rounded division), ll_out, pred_out (ties to the lowest component) and the determinism are scd_gmm_em_step's, word for word.
+ * nk_out double [k] = sum_i r_ik, s1c_out double [k, d] = sum_i r_ik c_ik, S_out double [k, d, d] = sum_i r_ik c_ik c_ik^T with
+ * S[k][j][l] and S[k][l][j] written from the same sum (bit-symmetric).
+ * a == Ut == NULL is the hard M-step (y and mu, the centres the moments are taken about, are still required): every row with a label
+ * in range contributes its one-hot times s_i, ll_out is 0 and pred_out is not written.
+ * The order: y is a float32 fma chain with l ascending from a zero accumulator (the float32-input MFMA), c one IEEE subtraction in a
+ * register; q a fmaf chain of the squares in an order fixed by d alone (docs/design/gmm_full.md), z = fmaf(-0.5, q, a_k); S
+ * accumulates r_ik c_ij (one float32 product) times c_il in float32 over chains of scd_gmm_full_chain_rows() rows and float64 across
+ * them, s1c and nk in float64 throughout.  No [n, k] logits reach memory, only r. */
+int scd_gmm_full_em_step(scd_handle h, const float* X, const int32_t* y, const float* sample_weight, int64_t n, int d, int k,
+                         const float* a, const float* mu, const float* Ut, double* ll_out, double* nk_out, double* s1c_out, double* S_out,
+                         int32_t* pred_out, int32_t* info_out, void* ws, size_t ws_bytes, void* stream);
+/* The forward pass alone, the same logits: pred_out int32 [n] or NULL, row_ll_out float32 [n] or NULL = lse_k z_ik, resp_out float32
+ * [n, k] or NULL = softmax_k(z_i), dense. */
+int scd_gmm_full_predict(scd_handle h, const float* X, int64_t n, int d, int k, const float* a, const float* mu, const float* Ut,
+                         int32_t* pred_out, float* row_ll_out, float* resp_out, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- principal component analysis: scikit-learn 1.7's PCA(svd_solver='covariance_eigh') without a centred or float64 copy of the rows
  *      (docs/design/pca.md).  Every call sees the rows as c_ij = fl32(x_ij - shift_j), one IEEE float32 subtraction in a register;
  *      shift float32 [d], or NULL for 0.  The eigensolver of the d x d matrix is the caller's. ---- */

@@ -66,7 +66,9 @@ def build_parser():
     p.add_argument('--cluster', type=str, default='KM', help='options: KM, SSKM, ConSSKM, FINCH (first-neighbour clustering refined to --n_cluster clusters), '
                                                                      'SC (spectral clustering on the exact k-NN graph, see --n_neighbors), '
                                                                      'HDBSCAN (no --n_cluster: the number of clusters is a result, see --min_cluster_size), '
-                                                                     'GMM (a diagonal Gaussian mixture of --n_cluster components, see --covariance_type)')
+                                                                     'GMM (a diagonal Gaussian mixture of --n_cluster components, see --covariance_type), '
+                                                                     'GMM_FULL, GMM_TIED (a covariance matrix per component, or one for all; rows of at '
+                                                                     'most 64 dimensions, see --pca_dim; --covariance_type is not read)')
     p.add_argument('--save_cluster', type=str2bool, default=False)
     p.add_argument('--n_cluster', type=int, default=1000)
     p.add_argument('--n_neighbors', type=int, default=10,
@@ -121,24 +123,35 @@ def pca_reduce(args, u_feats, l_feats):
     return tuple(pca.transform(x, unit=True).cpu().numpy() if len(x) else np.zeros((0, pca.n_components_), np.float32) for x in (u, l))
 
 
+FULL_COVARIANCE = {'GMM_FULL': 'full', 'GMM_TIED': 'tied'}                     # --cluster value -> FullGaussianMixture's covariance_type
+
+
 def run_gmm(args, u_feats, l_feats=None, l_targets=None):
-    """--cluster GMM (docs/design/gmm.md): scd_amd.gmm.GaussianMixture(n_cluster, covariance_type, random_state=0).  Without labelled
+    """--cluster GMM (docs/design/gmm.md): scd_amd.gmm.GaussianMixture(n_cluster, covariance_type, random_state=0); --cluster GMM_FULL |
+    GMM_TIED (docs/design/gmm_full.md): scd_amd.gmm_full.FullGaussianMixture(n_cluster, 'full' | 'tied', random_state=0).  Without labelled
     rows it is fitted on the unlabelled rows, as KM is.  With them (main_ptsup.py) the labelled rows come first, each clamped to the
     component of its class (the classes numbered in ascending order), and every row gets a label, as SSKM gives."""
-    from scd_amd.gmm import GaussianMixture
-    gm = GaussianMixture(n_components=args.n_cluster, covariance_type=args.covariance_type, random_state=0)
     u = np.asarray(u_feats, dtype=np.float32)
+    if args.cluster in FULL_COVARIANCE:
+        # docs/design/gmm_full.md: a covariance matrix per component (GMM_FULL) or one for all (GMM_TIED); --covariance_type is not read
+        from scd_amd.gmm_full import MAX_FEATURES, FullGaussianMixture
+        if u.shape[1] > MAX_FEATURES:
+            raise SystemExit(f"--cluster {args.cluster}: rows of {u.shape[1]} dimensions; pass --pca_dim M with M <= {MAX_FEATURES}")
+        gm = FullGaussianMixture(n_components=args.n_cluster, covariance_type=FULL_COVARIANCE[args.cluster], random_state=0)
+    else:
+        from scd_amd.gmm import GaussianMixture
+        gm = GaussianMixture(n_components=args.n_cluster, covariance_type=args.covariance_type, random_state=0)
     if l_feats is None:
         gm.fit(u)
-        print(f"GMM: {gm.n_iter_} iterations, converged {gm.converged_}, lower bound {gm.lower_bound_:.6f}, BIC {gm.bic(u):.1f}")
+        print(f"{args.cluster}: {gm.n_iter_} iterations, converged {gm.converged_}, lower bound {gm.lower_bound_:.6f}, BIC {gm.bic(u):.1f}")
         return None, gm.labels_
     classes, y_l = np.unique(np.asarray(l_targets), return_inverse=True)
     if len(classes) > args.n_cluster:
-        raise SystemExit(f"--cluster GMM: {len(classes)} labelled classes need --n_cluster >= {len(classes)} (got {args.n_cluster})")
+        raise SystemExit(f"--cluster {args.cluster}: {len(classes)} labelled classes need --n_cluster >= {len(classes)} (got {args.n_cluster})")
     x = np.concatenate([np.asarray(l_feats, dtype=np.float32), u])
     y = np.concatenate([y_l.astype(np.int64), np.full(len(u), -1, dtype=np.int64)])
     gm.fit(x, y)
-    print(f"GMM: {len(y_l)} rows clamped to {len(classes)} classes, {gm.n_iter_} iterations, converged {gm.converged_}, "
+    print(f"{args.cluster}: {len(y_l)} rows clamped to {len(classes)} classes, {gm.n_iter_} iterations, converged {gm.converged_}, "
           f"lower bound {gm.lower_bound_:.6f}")
     return gm.labels_, gm.labels_[len(y_l):]
 
@@ -167,7 +180,7 @@ def run_clustering(args, u_feats, l_feats, l_targets, semi_supervised=False):
         from scd_amd.spectral import SpectralClustering
         sc = SpectralClustering(n_clusters=args.n_cluster, n_neighbors=args.n_neighbors, random_state=0)
         return None, sc.fit_predict(np.asarray(u_feats, dtype=np.float32)).astype(np.int64)
-    elif args.cluster == 'GMM':
+    elif args.cluster == 'GMM' or args.cluster in FULL_COVARIANCE:
         return run_gmm(args, u_feats, l_feats, l_targets) if semi_supervised else run_gmm(args, u_feats)
     else:
         raise NotImplementedError(args.cluster)

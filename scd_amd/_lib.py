@@ -160,6 +160,13 @@ SIGNATURES = {
     "scd_gmm_em_step": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     # h, X, n, d, k, a, B, C, pred_out, row_ll_out, resp_out, ws, ws_bytes, stream
     "scd_gmm_predict": (_i, [_vp, _vp, _i64, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "scd_gmm_full_ws_bytes": (_sz, [_i64, _i, _i]),
+    "scd_gmm_full_row_tile": (_i, []),
+    "scd_gmm_full_chain_rows": (_i, []),
+    # h, X, y, sample_weight, n, d, k, a, mu, Ut, ll, nk, s1c, S, pred, info, ws, ws_bytes, stream
+    "scd_gmm_full_em_step": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    # h, X, n, d, k, a, mu, Ut, pred, row_ll, resp, ws, ws_bytes, stream
+    "scd_gmm_full_predict": (_i, [_vp, _vp, _i64, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "scd_pca_ws_bytes": (_sz, [_i64, _i, _i]),
     "scd_pca_row_tile": (_i, []),
     "scd_pca_chain_rows": (_i, []),

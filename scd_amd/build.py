@@ -16,7 +16,7 @@ LIB = os.path.join(LIBDIR, "libscd_hip.so")
 OBJDIR = os.path.join(LIBDIR, "obj")
 
 SOURCES = ["api.cpp", "munkres.cpp", "munkres_sparse.cpp", "transport.cpp", "hdbscan_tree.cpp", "comm.cpp", "kmeans.hip", "mstep.hip", "sim.hip", "vote.hip", "gemm.hip",
-           "encoder.hip", "image.hip", "jpeg.hip", "metrics.hip", "silhouette.hip", "finch.hip", "knn.hip", "tsne.hip", "probe.hip", "graph.hip", "hdbscan.hip", "gmm.hip", "pca.hip"]
+           "encoder.hip", "image.hip", "jpeg.hip", "metrics.hip", "silhouette.hip", "finch.hip", "knn.hip", "tsne.hip", "probe.hip", "graph.hip", "hdbscan.hip", "gmm.hip", "pca.hip", "gmm_full.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-atomics", "-Wno-unused-result",
          "-fno-gpu-rdc"]
@@ -30,7 +30,8 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-ato
 # probe.hip: the plain FLAGS - expf, logf and the division are the correctly rounded-to-2-ulp library forms its error model charges
 # gmm.hip: the plain FLAGS, for probe.hip's reason (its error model charges the same library forms)
 # pca.hip: the plain FLAGS, for probe.hip's reason (sqrtf and the division of its unit rows are the correctly rounded forms)
-# f32mm.h, which those three share, states the contract in its header comment: include it only from units built with the plain FLAGS
+# gmm_full.hip: the plain FLAGS, for probe.hip's reason (expf, logf and the division of its row softmax; its fmaf calls are written out)
+# f32mm.h, which those four share, states the contract in its header comment: include it only from units built with the plain FLAGS
 # tsne.hip: no contraction - its fused multiply-adds are written out, and its update step must be the IEEE operations numpy performs
 # graph.hip: no contraction - the sparse product's row sums are a multiply and an add per term, the order its contract states
 EXTRA = {"sim.hip": ["-fno-slp-vectorize"], "image.hip": ["-ffp-contract=off", "-fno-fast-math"], "tsne.hip": ["-ffp-contract=off"], "graph.hip": ["-ffp-contract=off"]}

@@ -60,10 +60,14 @@ def evaluate_k_unlabelled(K, feats, verbose=False, **kmeans_kw):
 
 
 def evaluate_k_bic(K, feats, covariance_type="diag", verbose=False, **gmm_kw):
-    """One K of the mixture search: fit `GaussianMixture(n_components=K, covariance_type, random_state=0)` (scd_amd.gmm) on feats (device
+    """One K of the mixture search: fit `GaussianMixture(n_components=K, covariance_type, random_state=0)` (scd_amd.gmm; scd_amd.gmm_full's
+    FullGaussianMixture for 'full' and 'tied') on feats (device
     float32 [n, d]) and take its BIC on the same rows: one n x K x d pass per EM step, no n x n pass.  The searches maximise, so the
     value returned is -BIC: (-bic, {'bic', 'lower_bound', 'n_iter', 'converged'})."""
-    from .gmm import GaussianMixture
+    if covariance_type in ("full", "tied"):                     # docs/design/gmm_full.md: rows of at most 64 dimensions
+        from .gmm_full import FullGaussianMixture as GaussianMixture
+    else:
+        from .gmm import GaussianMixture
     K = int(K)
     kw = dict(random_state=0)
     kw.update(gmm_kw)

@@ -107,8 +107,8 @@ class GaussianMixture:
             v = np.repeat(v[:, None], d, axis=1)
         return tuple(torch.as_tensor(np.ascontiguousarray(t), device=device) for t in (w, mu, v))
 
-    def _start(self, x, y, seed):
-        """The hard M-step on starting labels: k-means' (scd_amd.cluster.KMeans, one start) or seeded random ones; a labelled row
+    def _start_labels(self, x, y, seed):
+        """Starting labels int32 [n] on the device: k-means' (scd_amd.cluster.KMeans, one start) or seeded random ones; a labelled row
         keeps its class."""
         k = self.n_components
         if self.init_params == "kmeans":
@@ -131,7 +131,11 @@ class GaussianMixture:
                 perm[pairs[:, 0]] = pairs[:, 1]
                 lab = torch.as_tensor(perm.astype(np.int32), device=x.device)[lab.long()]
             lab = torch.where(y >= 0, y, lab)
-        _, nk, s1, s2, _, _ = ops.gmm_em_step(x, None, None, None, y=lab.contiguous(), n_components=k)
+        return lab.contiguous()
+
+    def _start(self, x, y, seed):
+        """The hard M-step on the starting labels."""
+        _, nk, s1, s2, _, _ = ops.gmm_em_step(x, None, None, None, y=self._start_labels(x, y, seed), n_components=self.n_components)
         return m_step(nk, s1, s2, self.covariance_type, self.reg_covar)
 
     # ------------------------------------------------------------------ the loop (scikit-learn's BaseMixture.fit_predict)
@@ -152,14 +156,31 @@ class GaussianMixture:
                 break
         return dict(w=w, mu=mu, v=v, lower=lower, trace=trace, converged=converged, n_iter=n_iter, info=info)
 
+    # ------------------------------------------------------------------ what a covariance family supplies (scd_amd.gmm_full overrides these)
+    def _check_features(self, d):
+        if d > 1024:
+            raise ValueError("at most 1024 features (got %d)" % d)
+
+    def _store(self, best):
+        """The fitted parameters of the best run: the kernel's operands and scikit-learn's attributes."""
+        self._w, self._mu, self._v = best["w"], best["mu"], best["v"]
+        self._abc = kernel_params(self._w, self._mu, self._v)
+        self.weights_ = self._w.cpu().numpy()
+        self.means_ = self._mu.cpu().numpy()
+        cov = self._v.cpu().numpy()
+        self.covariances_ = cov if self.covariance_type == "diag" else cov[:, 0].copy()
+        self.precisions_ = 1.0 / self.covariances_
+
+    def _kernel_forward(self, x, want_ll=False, want_resp=False):
+        return ops.gmm_predict(x, *self._abc, want_ll=want_ll, want_resp=want_resp)
+
     def fit(self, X, y=None):
         x = _as_device_f32(X)
         n, d = int(x.shape[0]), int(x.shape[1])
         k = self.n_components
         if n < k:
             raise ValueError("n_components = %d needs at least as many rows (got %d)" % (k, n))
-        if d > 1024:
-            raise ValueError("at most 1024 features (got %d)" % d)
+        self._check_features(d)
         yd = None
         if y is not None:
             y_np = np.asarray(y.cpu() if torch.is_tensor(y) else y)
@@ -181,18 +202,12 @@ class GaussianMixture:
         bad = best["info"].cpu().numpy()
         if bad[1]:
             warnings.warn("GaussianMixture: %d rows had a non-finite log-density at the last E-step" % bad[1])
-        self._w, self._mu, self._v = best["w"], best["mu"], best["v"]
-        self._abc = kernel_params(self._w, self._mu, self._v)
-        self.weights_ = self._w.cpu().numpy()
-        self.means_ = self._mu.cpu().numpy()
-        cov = self._v.cpu().numpy()
-        self.covariances_ = cov if self.covariance_type == "diag" else cov[:, 0].copy()
-        self.precisions_ = 1.0 / self.covariances_
+        self._store(best)
         self.converged_, self.n_iter_ = best["converged"], best["n_iter"]
         self.lower_bound_, self.lower_bounds_ = best["lower"], list(best["trace"])
         self.n_features_in_ = d
         # a final E-step makes the labels consistent with the parameters; a clamped row keeps its class
-        pred = ops.gmm_predict(x, *self._abc)[0]
+        pred = self._kernel_forward(x)[0]
         if yd is not None:
             pred = torch.where(yd >= 0, yd, pred)
         self.labels_device_ = pred
@@ -209,7 +224,7 @@ class GaussianMixture:
         x = _as_device_f32(X)
         if x.shape[1] != self.n_features_in_:
             raise ValueError("X has %d features, the fit had %d" % (x.shape[1], self.n_features_in_))
-        return ops.gmm_predict(x, *self._abc, want_ll=want_ll, want_resp=want_resp)
+        return self._kernel_forward(x, want_ll=want_ll, want_resp=want_resp)
 
     def predict(self, X):
         """The most likely component of each row, int64 on the device."""

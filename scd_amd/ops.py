@@ -1176,6 +1176,73 @@ def gmm_predict(x, a, b, c, want_ll=False, want_resp=False):
     return pred, row_ll, resp
 
 
+# ----------------------------------------------------------------------------- full-covariance mixtures (docs/design/gmm_full.md)
+def _gmm_full_params(who, x, a, mu, ut):
+    _need_cuda(x, a, mu, ut)
+    if x.dim() != 2 or x.dtype != torch.float32:
+        raise _lib.ScdError(_lib.SCD_EINVAL, who + ": x float32 [n, d]")
+    k, d = a.shape[0] if a.dim() == 1 else -1, x.shape[1]
+    if any(t.dtype != torch.float32 for t in (a, mu, ut)) or k < 1 or mu.shape != (k, d) or ut.shape != (k, d, d):
+        raise _lib.ScdError(_lib.SCD_EINVAL, who + ": a float32 [k], mu float32 [k, d], ut float32 [k, d, d]")
+    return x.contiguous(), a.contiguous(), mu.contiguous(), ut.contiguous()
+
+
+def gmm_full_em_step(x, a, mu, ut, y=None, sample_weight=None, want_pred=False):
+    """scd_gmm_full_em_step: x float32 [n, d <= 64]; a float32 [k], mu float32 [k, d], ut float32 [k, d, d] with ut[k, j, l] =
+    U_k[l, j] (U_k the upper-triangular precision factor; z_ik = a_k - 0.5 |(x_i - mu_k) U_k|^2); y int32 [n] or None (a row with
+    0 <= y_i < k is clamped to its class); sample_weight float32 [n] or None -> (ll float64 [1], nk float64 [k], s1c float64 [k, d] =
+    sum_i r_ik (x_i - mu_k), S float64 [k, d, d] = sum_i r_ik (x_i - mu_k)(x_i - mu_k)^T, pred int32 [n] or None, info int32 [2]), all
+    on the device.  With a = ut = None it is the hard M-step about the centres mu: the labelled rows' one-hots alone, ll = 0, no pred."""
+    hard = a is None and ut is None
+    if hard:
+        _need_cuda(x, mu)
+        if (x.dim() != 2 or x.dtype != torch.float32 or mu is None or mu.dtype != torch.float32 or mu.dim() != 2 or mu.shape[0] < 1
+                or mu.shape[1] != x.shape[1] or y is None or want_pred):
+            raise _lib.ScdError(_lib.SCD_EINVAL, "gmm_full_em_step: the hard M-step takes x float32 [n, d], mu float32 [k, d], y and no pred")
+        x, mu = x.contiguous(), mu.contiguous()
+    else:
+        if a is None or ut is None or mu is None:
+            raise _lib.ScdError(_lib.SCD_EINVAL, "gmm_full_em_step: a and ut are both given or both None")
+        x, a, mu, ut = _gmm_full_params("gmm_full_em_step", x, a, mu, ut)
+    (n, d), k = x.shape, mu.shape[0]
+    if y is not None:
+        _need_cuda(y)
+        if y.dtype != torch.int32 or y.shape != (n,):
+            raise _lib.ScdError(_lib.SCD_EINVAL, "gmm_full_em_step: y int32 [n]")
+        y = y.contiguous()
+    if sample_weight is not None:
+        _need_cuda(sample_weight)
+        if sample_weight.dtype != torch.float32 or sample_weight.shape != (n,):
+            raise _lib.ScdError(_lib.SCD_EINVAL, "gmm_full_em_step: sample_weight float32 [n]")
+        sample_weight = sample_weight.contiguous()
+    ll = torch.empty(1, dtype=torch.float64, device=x.device)
+    nk = torch.empty(k, dtype=torch.float64, device=x.device)
+    s1c = torch.empty((k, d), dtype=torch.float64, device=x.device)
+    S = torch.empty((k, d, d), dtype=torch.float64, device=x.device)
+    pred = torch.empty(n, dtype=torch.int32, device=x.device) if want_pred else None
+    info = torch.empty(2, dtype=torch.int32, device=x.device)
+    nb = _L().scd_gmm_full_ws_bytes(n, d, k)
+    ws = _ws(max(nb, 16), x.device)
+    check(_L().scd_gmm_full_em_step(handle(), ptr(x), ptr(y), ptr(sample_weight), n, d, k, ptr(a), ptr(mu), ptr(ut), ptr(ll), ptr(nk),
+                                    ptr(s1c), ptr(S), ptr(pred), ptr(info), ptr(ws), nb, stream_ptr()))
+    return ll, nk, s1c, S, pred, info
+
+
+def gmm_full_predict(x, a, mu, ut, want_ll=False, want_resp=False):
+    """scd_gmm_full_predict: x float32 [n, d <= 64], a float32 [k], mu float32 [k, d], ut float32 [k, d, d] -> (pred int32 [n], ties to
+    the lowest component; row_ll float32 [n] = lse_k z_ik or None; resp float32 [n, k] = softmax_k(z_i) or None)."""
+    x, a, mu, ut = _gmm_full_params("gmm_full_predict", x, a, mu, ut)
+    (n, d), k = x.shape, a.shape[0]
+    pred = torch.empty(n, dtype=torch.int32, device=x.device)
+    row_ll = torch.empty(n, dtype=torch.float32, device=x.device) if want_ll else None
+    resp = torch.empty((n, k), dtype=torch.float32, device=x.device) if want_resp else None
+    nb = _L().scd_gmm_full_ws_bytes(1, d, k)
+    ws = _ws(max(nb, 16), x.device)
+    check(_L().scd_gmm_full_predict(handle(), ptr(x), n, d, k, ptr(a), ptr(mu), ptr(ut), ptr(pred), ptr(row_ll), ptr(resp), ptr(ws), nb,
+                                    stream_ptr()))
+    return pred, row_ll, resp
+
+
 # ----------------------------------------------------------------------------- principal components (docs/design/pca.md)
 def _pca_args(who, x, shift):
     _need_cuda(x, shift)
