@@ -18,6 +18,11 @@
 //     two calls return the same bits on any device.
 //   - include only from units built with the plain flags (scd_amd/build.py): the error models charge the library forms of expf, logf,
 //     sqrtf and the division, and contraction must stay at the compiler's default.
+//
+// tests/f32mm_plan.py restates the host side below in plain Python: f32mm_ranges, f32mm_colsum_ranges, f32mm_fwd_dispatch, each unit's
+// tile count and its workspace layout.  tests/test_f32mm_plan_host.py holds the four scd_*_ws_bytes to it (they depend on R and RB, so
+// they pin the plans the kernels are launched with) and names the regime of every device case: the cap of 32 ranges, a last range of
+// one row, the column sums' cap of 64 ranges, NT = 2 and NT = 8 with phantom tiles.  A change to a plan here is a change there.
 #pragma once
 #include <type_traits>
 

@@ -3,6 +3,8 @@ cases and the planted mistakes.  docs/design/gmm.md derives the bounds.  Everyth
 device receives, so the only difference a test sees is the device's rounding."""
 import numpy as np
 
+import f32mm_plan as fp
+
 U = 2.0 ** -24                                  # unit roundoff of float32
 TINY = 2.0 ** -126                              # smallest normal float32: the absolute floor of an underflowing e
 ROW_TILE = 32                                   # scd_gmm_row_tile(); the host test asserts the library agrees
@@ -77,13 +79,26 @@ def em_step_f64(X, y, a, B, C, sw=None, mistake=None):
     keep = np.ones(n, bool)
     if mistake == "ragged_tile_dropped":
         keep[n // ROW_TILE * ROW_TILE:] = False
+    plan = fp.gmm_plan(n, d, k)
+    if mistake == "last_range_dropped":
+        keep[(plan["R"] - 1) * plan["rows"]:] = False
     mult = keep.astype(np.float64)
     if mistake == "chain_row_twice" and n > CHAIN_ROWS:
         mult[CHAIN_ROWS - 1] = 2.0
+    if mistake == "range_added_twice":
+        mult[plan["rows"]:2 * plan["rows"]] = 2.0
     rm = r * mult[:, None]
-    nk = (resp * mult[:, None]).sum(axis=0) if mistake == "weight_ignored" else rm.sum(axis=0)
+    mult_cs = mult.copy()
+    if mistake == "colsum_range_tail_dropped":                  # a column-sum range loses the rows past its last whole group of eight
+        for lo, hi in fp.range_bounds(n, plan["RB"], plan["cs_rows"]):
+            mult_cs[hi - (hi - lo) % fp.CS_GROUPS:hi] = 0.0
+    nk = (resp * mult[:, None]).sum(axis=0) if mistake == "weight_ignored" else (r * mult_cs[:, None]).sum(axis=0)
     s1 = rm.T @ X64
     s2 = rm.T @ (X64 if mistake == "x_for_x2_in_s2" else X2)
+    if mistake == "range_stride_of_one_tile":                   # every tile but the first reads range 0's partial R times
+        first = (np.arange(k)[:, None] < fp.GT) & (np.arange(d)[None, :] < fp.GT)
+        r0 = plan["R"] * r[:plan["rows"]].T
+        s1, s2 = np.where(first, s1, r0 @ X64[:plan["rows"]]), np.where(first, s2, r0 @ X2[:plan["rows"]])
     pred = (k - 1 - np.argmax(z[:, ::-1], axis=1)) if mistake == "ties_to_highest" else np.argmax(z, axis=1)
     info = np.array([int((yy >= k).sum()), int((~np.isfinite(z)).any(axis=1).sum())])
     return dict(ll=float((rowll * keep).sum()), nk=nk, s1=s1, s2=s2, pred=pred.astype(np.int64), info=info, z=z, lse=lse, p=p, r=r, s=s,
@@ -180,13 +195,23 @@ def shapes():
     rt, T = ROW_TILE, CHAIN_ROWS
     return {"n1_d1_k1": (1, 1, 1), "ragged_tile": (rt - 1, 5, 3), "k33": (rt + 1, 64, 33), "d768_k100": (3 * rt + 7, 768, 100),
             "full_width": (2 * rt, 1024, 1024), "two_chains": (T + 1, 96, 31), "four_chains": (3 * T + 5, 33, 257),
-            "two_ranges": (9 * T + 3, 33, 33)}                  # the last: R = 2 row ranges of several chains each in the moments
+            "two_ranges": (9 * T + 3, 33, 33),                  # R = 2 row ranges of several chains each in the moments
+            # the forward kernel's NT = 2 and NT = 8 with phantom tiles, then the range plans (tests/f32mm_plan.py has each regime)
+            **{name: shape for name, (shape, _) in fp.NT_CASES.items()},
+            **{name: c["wide"] for name, c in fp.RANGE_CASES.items() if "wide" in c}}
 
 
 VARIANTS = ("unlabelled", "mixed", "all_labelled", "hard", "weights", "bad_labels")
-# chosen so that in every variant every row's top-two gap exceeds 2 delta (tests/test_gmm_host.py asserts it): no row is excused
+LARGE_VARIANTS = ("unlabelled", "weights", "hard")              # of the cases with n >= f32mm_plan.LARGE_N: the rest do not bear on the ranges
+# chosen so that in every variant every row's top-two gap exceeds 2 delta (tests/test_gmm_host.py asserts it): no row is excused.  The
+# cases with n >= f32mm_plan.LARGE_N keep the default seed and carry an undecided_cap instead: of 10^4 - 10^5 random rows one or two have
+# a gap within 2 delta, and predictions do not depend on the ranges
 SHAPE_SEEDS = {"n1_d1_k1": 2000, "ragged_tile": 2000, "k33": 2000, "d768_k100": 2000, "full_width": 2000, "two_chains": 2000,
                "four_chains": 2000, "two_ranges": 2000}
+
+
+def variants_of(name, menu=None):
+    return LARGE_VARIANTS if (menu or shapes())[name][0] >= fp.LARGE_N else VARIANTS
 
 
 def _mixed_labels(case, rng):
@@ -203,7 +228,8 @@ def _mixed_labels(case, rng):
 
 def shape_case(name, variant="unlabelled"):
     n, d, k = shapes()[name]
-    case = mixture(n, d, k, seed=SHAPE_SEEDS[name])
+    case = mixture(n, d, k, seed=SHAPE_SEEDS.get(name, 2000))
+    case["undecided_cap"] = fp.undecided_cap(n)
     rng = np.random.default_rng(78)
     if variant in ("mixed", "hard", "weights", "bad_labels"):
         case["y"] = _mixed_labels(case, rng)
@@ -218,7 +244,7 @@ def shape_case(name, variant="unlabelled"):
             sw[:] = 0.75
         case["sw"] = sw
     elif variant == "bad_labels":                               # two more rows, labels k and k + 5: they count as unlabelled
-        extra = mixture(2, d, k, seed=SHAPE_SEEDS[name])["X"]
+        extra = mixture(2, d, k, seed=SHAPE_SEEDS.get(name, 2000))["X"]
         case["X"] = np.concatenate([case["X"][: n // 2], extra[:1], case["X"][n // 2:], extra[1:]])
         case["y"] = np.concatenate([case["y"][: n // 2], [k], case["y"][n // 2:], [k + 5]]).astype(np.int32)
         case["truth"] = np.concatenate([case["truth"][: n // 2], [0], case["truth"][n // 2:], [0]])
@@ -296,7 +322,7 @@ def special_cases():
 def all_cases():
     out = {}
     for name in shapes():
-        for v in VARIANTS:
+        for v in variants_of(name):
             out["%s-%s" % (name, v)] = shape_case(name, v)
     out.update(special_cases())
     return out
@@ -322,7 +348,18 @@ MISTAKES = {
     "ragged_tile_dropped": "ragged_tile-unlabelled",
     "chain_row_twice": "two_chains-unlabelled",
     "ties_to_highest": "identical",
+    "last_range_dropped": "ranges_x_tiles-unlabelled",          # a last range of ONE row
+    "range_added_twice": "cap32-unlabelled",
+    "range_stride_of_one_tile": "ranges_x_tiles-unlabelled",
+    "colsum_range_tail_dropped": "colsum_cap-unlabelled",
 }
+# the mistakes that must show on further cases as well
+ALSO = [("padding_in_sum", "nt2_phantom-unlabelled"), ("padding_in_sum", "nt8_phantom-unlabelled")]
+RANGE_MISTAKES = ("last_range_dropped", "range_added_twice", "range_stride_of_one_tile", "colsum_range_tail_dropped")
+
+
+def mistake_cases():
+    return list(MISTAKES.items()) + ALSO
 
 
 def planted(case, mistake):

@@ -4,7 +4,8 @@ evaluated at the SAME float32 X, a, mu, Ut the device receives, the centred rows
 them, so the only difference a test sees is the device's rounding."""
 import numpy as np
 
-from gmm_cases import EPS64, TINY, U, _mixed_labels, decided_rows, gamma, ratio, shift, top2_gap  # noqa: F401
+import f32mm_plan as fp
+from gmm_cases import EPS64, TINY, U, _mixed_labels, decided_rows, gamma, ratio, shift, top2_gap, variants_of  # noqa: F401
 
 ROW_TILE = 32                                   # scd_gmm_full_row_tile(); the host test asserts the library agrees
 CHAIN_ROWS = 256                                # scd_gmm_full_chain_rows()
@@ -93,11 +94,28 @@ def em_step_f64(X, y, a, mu, Ut, sw=None, mistake=None):
     keep = np.ones(n, bool)
     if mistake == "ragged_tile_dropped":
         keep[n // ROW_TILE * ROW_TILE:] = False
+    plan = fp.gmm_full_plan(n, d, k)
+    if mistake == "last_range_dropped":
+        keep[(plan["R"] - 1) * plan["rows"]:] = False
     mult = keep.astype(np.float64)
     if mistake == "chain_row_twice" and n > CHAIN_ROWS:
         mult[CHAIN_ROWS - 1] = 2.0
+    if mistake == "range_added_twice":
+        mult[plan["rows"]:2 * plan["rows"]] = 2.0
     rm = r * mult[:, None]
     st = _moments(rm, c, X64, mult, mistake)
+    if mistake == "colsum_range_tail_dropped":                  # a column-sum range loses the rows past its last whole group of eight
+        mult_cs = mult.copy()
+        for lo, hi in fp.range_bounds(n, plan["RB"], plan["cs_rows"]):
+            mult_cs[hi - (hi - lo) % fp.CS_GROUPS:hi] = 0.0
+        st["nk"] = (r * mult_cs[:, None]).sum(axis=0)
+    if mistake == "range_stride_of_one_tile":                   # every moment block but the first reads range 0's partial R times
+        rows = plan["rows"]
+        alt = _moments(plan["R"] * rm[:rows], c[:rows], X64[:rows])
+        st["S"][fp.GMMF_CG:], st["s1c"][fp.GMMF_CG:] = alt["S"][fp.GMMF_CG:], alt["s1c"][fp.GMMF_CG:]
+    if mistake == "second_j_tile_first_chain_only":             # the accumulators of the second j-tile carried into float64 once
+        alt = _moments(rm[:CHAIN_ROWS], c[:CHAIN_ROWS], X64[:CHAIN_ROWS])
+        st["S"][:, 32:, :], st["S"][:, :, 32:], st["s1c"][:, 32:] = alt["S"][:, 32:, :], alt["S"][:, :, 32:], alt["s1c"][:, 32:]
     info = np.array([int((yy >= k).sum()), int((~np.isfinite(z)).any(axis=1).sum())])
     st.update(ll=float((rowll * keep).sum()), pred=np.argmax(z, axis=1).astype(np.int64), info=info, z=z, lse=lse, p=p, r=r, s=s, lab=lab,
               rowll=rowll, c=c, y=yv, q=q)
@@ -214,18 +232,22 @@ def shapes():
     rt, T = ROW_TILE, CHAIN_ROWS
     return {"n1_d1_k1": (1, 1, 1), "ragged_tile": (rt - 1, 5, 3), "one_j_tile": (rt + 1, 32, 33), "ragged_j_tile": (3 * rt + 7, 33, 5),
             "full_width": (2 * rt, 64, 1024), "two_chains": (T + 1, 24, 31), "four_chains": (3 * T + 5, 8, 257),
-            "ranges": (9 * T + 3, 17, 9)}                       # the last: several row ranges of several chains each in the moments
+            "ranges": (9 * T + 3, 17, 9),                       # several row ranges of several chains each in the moments
+            # JT = 2 across chains, then the range plans (tests/f32mm_plan.py has each regime)
+            **{name: c["full"] for name, c in fp.RANGE_CASES.items()}}
 
 
 VARIANTS = ("unlabelled", "mixed", "all_labelled", "hard", "weights", "bad_labels")
-# chosen so that in every variant every row's top-two gap exceeds 2 delta (tests/test_gmm_full_host.py asserts it): no row is excused
+# chosen so that in every variant every row's top-two gap exceeds 2 delta (tests/test_gmm_full_host.py asserts it): no row is excused.  The
+# cases with n >= f32mm_plan.LARGE_N run in gmm_cases.LARGE_VARIANTS, keep the default seed and carry an undecided_cap instead
 SHAPE_SEEDS = {"n1_d1_k1": 2000, "ragged_tile": 2000, "one_j_tile": 2000, "ragged_j_tile": 2000, "full_width": 2000, "two_chains": 2000,
                "four_chains": 2000, "ranges": 2000}
 
 
 def shape_case(name, variant="unlabelled"):
     n, d, k = shapes()[name]
-    case = mixture(n, d, k, seed=SHAPE_SEEDS[name])
+    case = mixture(n, d, k, seed=SHAPE_SEEDS.get(name, 2000))
+    case["undecided_cap"] = fp.undecided_cap(n)
     rng = np.random.default_rng(78)
     if variant in ("mixed", "hard", "weights", "bad_labels"):
         case["y"] = _mixed_labels(case, rng)
@@ -240,7 +262,7 @@ def shape_case(name, variant="unlabelled"):
             sw[:] = 0.75
         case["sw"] = sw
     elif variant == "bad_labels":                               # two more rows, labels k and k + 5: they count as unlabelled
-        extra = mixture(2, d, k, seed=SHAPE_SEEDS[name])["X"]
+        extra = mixture(2, d, k, seed=SHAPE_SEEDS.get(name, 2000))["X"]
         case["X"] = np.concatenate([case["X"][: n // 2], extra[:1], case["X"][n // 2:], extra[1:]])
         case["y"] = np.concatenate([case["y"][: n // 2], [k], case["y"][n // 2:], [k + 5]]).astype(np.int32)
         case["truth"] = np.concatenate([case["truth"][: n // 2], [0], case["truth"][n // 2:], [0]])
@@ -316,7 +338,7 @@ def special_cases():
 def all_cases():
     out = {}
     for name in shapes():
-        for v in VARIANTS:
+        for v in variants_of(name, shapes()):
             out["%s-%s" % (name, v)] = shape_case(name, v)
     out.update(special_cases())
     return out
@@ -343,7 +365,14 @@ MISTAKES = {
     "ragged_tile_dropped": "ragged_tile-unlabelled",
     "padding_in_sum": "far_rows",
     "labelled_softmax": "least_likely_label",
+    "last_range_dropped": "ranges_x_tiles-unlabelled",          # a last range of ONE row
+    "range_added_twice": "cap32-unlabelled",
+    "range_stride_of_one_tile": "ranges_x_tiles-unlabelled",
+    "colsum_range_tail_dropped": "colsum_cap-unlabelled",
+    "second_j_tile_first_chain_only": "jt2_chains-unlabelled",
 }
+RANGE_MISTAKES = ("last_range_dropped", "range_added_twice", "range_stride_of_one_tile", "colsum_range_tail_dropped",
+                  "second_j_tile_first_chain_only")
 # planted mistakes of the M-step: shown against scikit-learn's parameters (tests/test_gmm_full_host.py)
 M_STEP_MISTAKES = ("cross_term_sign", "reg_off_diagonal", "tied_over_k")
 

@@ -4,6 +4,8 @@ c = fl32(x - a) the device forms (one IEEE subtraction, which numpy float32 repr
 is the device's rounding."""
 import numpy as np
 
+import f32mm_plan as fp
+
 U = 2.0 ** -24                                  # unit roundoff of float32
 EPS64 = float(np.finfo(np.float64).eps)
 ROW_TILE = 32                                   # scd_pca_row_tile(); the host test asserts the library agrees
@@ -43,7 +45,14 @@ def rounded_mean(X):
 def colsum_f64(X, a, mistake=None):
     if mistake == "csum_from_x":
         return np.asarray(X, np.float64).sum(axis=0)
-    return centred(X, a, mistake).sum(axis=0)
+    c = centred(X, a, mistake)
+    if mistake == "colsum_range_tail_dropped":                  # a column-sum range loses the rows past its last whole group of eight
+        n = c.shape[0]
+        keep = np.ones(n)
+        for lo, hi in fp.range_bounds(n, *fp.colsum_ranges(n)):
+            keep[hi - (hi - lo) % fp.CS_GROUPS:hi] = 0.0
+        return (c * keep[:, None]).sum(axis=0)
+    return c.sum(axis=0)
 
 
 def gram_f64(X, a, mistake=None):
@@ -55,7 +64,15 @@ def gram_f64(X, a, mistake=None):
         mult[n // ROW_TILE * ROW_TILE:] = 0.0
     if mistake == "chain_row_twice" and n > CHAIN_ROWS:
         mult[CHAIN_ROWS - 1] = 2.0
+    plan = fp.pca_plan(n, d)
+    if mistake == "last_range_dropped":
+        mult[(plan["R"] - 1) * plan["rows"]:] = 0.0
+    if mistake == "range_added_twice":
+        mult[plan["rows"]:2 * plan["rows"]] = 2.0
     G = (c * mult[:, None]).T @ c
+    if mistake == "range_stride_of_one_tile":                   # every tile but the first reads range 0's partial R times
+        first = (np.arange(d)[:, None] < TILE) & (np.arange(d)[None, :] < TILE)
+        G = np.where(first, G, plan["R"] * (c[:plan["rows"]].T @ c[:plan["rows"]]))
     tiles = [(s, min(s + TILE, d)) for s in range(0, d, TILE)]
     if mistake == "diag_tile_twice":
         for lo, hi in tiles:
@@ -117,11 +134,8 @@ def fit_f64(X, a, n_components=None, whiten=False, mistake=None):
 
 def phantom_columns(m):
     """Columns a block computes beyond the padded width mp = m up to 32: four waves take NT = 1, 2, 4 or 8 tiles each; a tile past mp
-    repeats the packed row mp - 1 (a real column only when m == mp)."""
-    mp = -(-m // 32) * 32
-    per = -(-(mp // 32) // 4)
-    nt = 1 if per <= 1 else 2 if per <= 2 else 4 if per <= 4 else 8
-    return 4 * nt * 32 - mp, mp
+    repeats the packed row mp - 1 (a real column only when m == mp).  tests/f32mm_plan.py restates the dispatch."""
+    return fp.phantom_columns(m)
 
 
 def transform_f64(X, a, W, unit=False, mistake=None):
@@ -132,9 +146,10 @@ def transform_f64(X, a, W, unit=False, mistake=None):
         return y
     ss = (y * y).sum(axis=1)
     if mistake == "unit_over_padded":
+        # every column of the block past m repeats the last real column and is counted.  With m == mp that is the kernel's own clamp to
+        # the packed row mp - 1 with the mask left out; with m < mp it is that clamp taken to m - 1 instead (the row mp - 1 is zero)
         extra, mp = phantom_columns(y.shape[1])
-        if mp == y.shape[1]:
-            ss = ss + extra * y[:, -1] ** 2
+        ss = ss + (extra + mp - y.shape[1]) * y[:, -1] ** 2
     nrm = np.sqrt(ss)
     with np.errstate(invalid="ignore", divide="ignore"):
         return np.where(nrm[:, None] == 0.0, 0.0, y / nrm[:, None])
@@ -220,9 +235,13 @@ def unit_rows(n, d, seed):
     return np.ascontiguousarray(z, dtype=np.float32)
 
 
-GRAM_SHAPES = [(1, 1), (31, 5), (33, 64), (T + 1, 96), (3 * T + 5, 129), (9 * T + 3, 33), (64, 1024), (231, 768)]
+# the range plans and the forward regimes of tests/f32mm_plan.py, by name
+NAMED_GRAM = {name: c["gram"] for name, c in fp.RANGE_CASES.items() if "gram" in c}
+NAMED_TRANSFORM = {**{name: shape for name, (shape, _) in fp.NT_CASES.items()}, "ranges_x_tiles": fp.RANGE_CASES["ranges_x_tiles"]["wide"]}
+GRAM_SHAPES = [(1, 1), (31, 5), (33, 64), (T + 1, 96), (3 * T + 5, 129), (9 * T + 3, 33), (64, 1024), (231, 768)] + list(NAMED_GRAM.values())
 TRANSFORM_SHAPES = [(1, 1, 1), (31, 5, 3), (33, 64, 33), (231, 768, 100), (64, 1024, 1024), (257, 96, 31), (70, 33, 257),
-                    (40, 16, 32)]               # the last one: m == mp and three waves on tiles past mp (unit_over_padded shows there)
+                    (40, 16, 32)                # m == mp and three waves on tiles past mp (unit_over_padded shows there)
+                    ] + list(NAMED_TRANSFORM.values())
 FIT_SHAPES = [(1500, 64, 8), (2000, 96, 16), (1200, 33, 4)]
 
 
@@ -326,4 +345,15 @@ MISTAKES = {
     "unit_over_padded": ("the unit norm taken over the padded columns of an unmasked accumulator", transform_name(40, 16, 32, "unit"),
                          "transform"),
     "no_correction": ("the correction csum csum^T / n omitted", fit_name(1200, 33, 4) + "-shift0", "weyl"),
+    "last_range_dropped": ("the last range (ONE row) left out", gram_name(*NAMED_GRAM["ranges_x_tiles"], True), "gram"),
+    "range_added_twice": ("the second range's partial counted twice", gram_name(*NAMED_GRAM["cap32"], True), "gram"),
+    "range_stride_of_one_tile": ("a partial stride that forgets the tile count", gram_name(*NAMED_GRAM["ranges_x_tiles"], True), "gram"),
+    "colsum_range_tail_dropped": ("the last rows % 8 rows of each column-sum range left out", gram_name(*NAMED_GRAM["colsum_cap"], False),
+                                  "colsum"),
 }
+# the mistakes that must show on further cases as well: (mistake, case, kind)
+ALSO = [("unit_over_padded", transform_name(*NAMED_TRANSFORM[name], "unit"), "transform") for name in ("nt2_phantom", "nt8_phantom")]
+
+
+def mistake_cases():
+    return [(m, case, kind) for m, (_, case, kind) in MISTAKES.items()] + ALSO

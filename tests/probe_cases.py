@@ -5,6 +5,8 @@ import warnings
 
 import numpy as np
 
+import f32mm_plan as fp
+
 U = 2.0 ** -24                                  # unit roundoff of float32
 TINY = 2.0 ** -126                              # smallest normal float32: the absolute floor of an underflowing e (docs/design/probe.md)
 ROW_TILE = 32                                   # scd_probe_row_tile(); the host test asserts the library agrees
@@ -57,12 +59,24 @@ def loss_grad_f64(X, y, W, b=None, sw=None, mistake=None):
     keep = np.ones(n, bool)
     if mistake == "ragged_tile_dropped":
         keep[n // ROW_TILE * ROW_TILE:] = False
+    plan = fp.probe_plan(n, d, c)
+    if mistake == "last_range_dropped":
+        keep[(plan["R"] - 1) * plan["rows"]:] = False
     mult = keep.astype(np.float64)
     if mistake == "chain_row_twice" and n > CHAIN_ROWS:
         mult[CHAIN_ROWS - 1] = 2.0
+    if mistake == "range_added_twice":
+        mult[plan["rows"]:2 * plan["rows"]] = 2.0
     loss = float((rowloss * keep).sum())
     gW = (r * mult[:, None]).T @ X64
-    gb = ((p - onehot) * ok[:, None] * keep[:, None]).sum(axis=0) if mistake == "gb_unweighted" else (r * keep[:, None]).sum(axis=0)
+    if mistake == "range_stride_of_one_tile":                   # every tile but the first reads range 0's partial R times
+        first = (np.arange(c)[:, None] < fp.GT) & (np.arange(d)[None, :] < fp.GT)
+        gW = np.where(first, gW, plan["R"] * (r[:plan["rows"]].T @ X64[:plan["rows"]]))
+    keep_cs = keep.copy()
+    if mistake == "colsum_range_tail_dropped":                  # a column-sum range loses the rows past its last whole group of eight
+        for lo, hi in fp.range_bounds(n, plan["RB"], plan["cs_rows"]):
+            keep_cs[hi - (hi - lo) % fp.CS_GROUPS:hi] = False
+    gb = ((p - onehot) * ok[:, None] * keep[:, None]).sum(axis=0) if mistake == "gb_unweighted" else (r * keep_cs[:, None]).sum(axis=0)
     pred = (c - 1 - np.argmax(z[:, ::-1], axis=1)) if mistake == "ties_to_highest" else np.argmax(z, axis=1)
     info = np.array([int((~ok).sum()), int((~np.isfinite(z)).any(axis=1).sum())])
     return dict(loss=loss, gW=gW, gb=gb, pred=pred.astype(np.int64), info=info, z=z, lse=lse, p=p, r=r, s=s, ok=ok)
@@ -145,18 +159,29 @@ def shapes():
     rt, T = ROW_TILE, CHAIN_ROWS
     return {"n1_d1_c2": (1, 1, 2), "ragged_tile": (rt - 1, 5, 3), "c33": (rt + 1, 64, 33), "d768_c100": (3 * rt + 7, 768, 100),
             "full_width": (2 * rt, 1024, 1024), "two_chains": (T + 1, 96, 31), "four_chains": (3 * T + 5, 33, 257),
-            "two_ranges": (9 * T + 3, 33, 33)}                  # the last: R = 2 row ranges of several chains each in the gradient
+            "two_ranges": (9 * T + 3, 33, 33),                  # R = 2 row ranges of several chains each in the gradient
+            # the forward kernel's NT = 2 and NT = 8 with phantom tiles, then the range plans (tests/f32mm_plan.py has each regime)
+            **{name: shape for name, (shape, _) in fp.NT_CASES.items()},
+            **{name: c["wide"] for name, c in fp.RANGE_CASES.items() if "wide" in c}}
 
 
 VARIANTS = ("base", "weights", "no_bias", "bad_labels")
-# chosen so that in every variant every row's top-two gap exceeds 2 delta (tests/test_probe_host.py asserts it): no row is excused
+LARGE_VARIANTS = ("base", "weights")            # of the cases with n >= f32mm_plan.LARGE_N: the variants do not bear on the range plans
+# chosen so that in every variant every row's top-two gap exceeds 2 delta (tests/test_probe_host.py asserts it): no row is excused.  The
+# cases with n >= f32mm_plan.LARGE_N keep the default seed and carry an undecided_cap instead: of 10^4 - 10^5 random rows a few have a
+# gap within 2 delta, and predictions do not depend on the ranges
 SHAPE_SEEDS = {"n1_d1_c2": 1000, "ragged_tile": 1000, "c33": 1000, "d768_c100": 1002, "full_width": 1000, "two_chains": 1000,
                "four_chains": 1000, "two_ranges": 1000}
 
 
+def variants_of(name):
+    return LARGE_VARIANTS if shapes()[name][0] >= fp.LARGE_N else VARIANTS
+
+
 def shape_case(name, variant="base"):
     n, d, c = shapes()[name]
-    case = base_case(n, d, c, seed=SHAPE_SEEDS[name])
+    case = base_case(n, d, c, seed=SHAPE_SEEDS.get(name, 1000))
+    case["undecided_cap"] = fp.undecided_cap(n)
     rng = np.random.default_rng(77)
     if variant == "weights":
         sw = rng.uniform(0.25, 2.0, n).astype(np.float32)
@@ -222,7 +247,7 @@ def special_cases():
 def all_cases():
     out = {}
     for name in shapes():
-        for v in VARIANTS:
+        for v in variants_of(name):
             out["%s-%s" % (name, v)] = shape_case(name, v)
     out.update(special_cases())
     return out
@@ -239,7 +264,17 @@ MISTAKES = {
     "gb_unweighted": "c33-weights",
     "ties_to_highest": "ties",
     "chain_row_twice": "two_chains-base",
+    "last_range_dropped": "ranges_x_tiles-base",                # a last range of ONE row
+    "range_added_twice": "cap32-base",
+    "range_stride_of_one_tile": "ranges_x_tiles-base",
+    "colsum_range_tail_dropped": "colsum_cap-base",
 }
+# the mistakes that must show on further cases as well
+ALSO = [("padding_in_sum", "nt2_phantom-base"), ("padding_in_sum", "nt8_phantom-base")]
+
+
+def mistake_cases():
+    return list(MISTAKES.items()) + ALSO
 
 
 # ------------------------------------------------------------------------------------------------- the fit, restated

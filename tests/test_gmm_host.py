@@ -6,6 +6,7 @@ import re
 import numpy as np
 import pytest
 
+import f32mm_plan as fp
 import gmm_cases as gc
 
 GIB = 1 << 30
@@ -99,7 +100,9 @@ def test_no_row_is_excused(name):
     case = CASES[name]
     bd = gc.bounds(case["X"], case["y"], case["a"], case["B"], case["C"], case["sw"])
     dec = gc.decided_rows(bd, case["exact_ties"])
-    assert dec.all(), "rows %s have a top-two gap within 2 delta" % np.flatnonzero(~dec)
+    cap = case.get("undecided_cap", 0.0)                        # 0 below f32mm_plan.LARGE_N rows: no row is excused there
+    assert cap == (fp.UNDECIDED_CAP if case["X"].shape[0] >= fp.LARGE_N else 0.0)
+    assert (~dec).mean() <= cap, "rows %s have a top-two gap within 2 delta" % np.flatnonzero(~dec)
 
 
 def test_variants_differ_only_where_they_should():
@@ -119,12 +122,16 @@ def test_variants_differ_only_where_they_should():
 
 
 # ------------------------------------------------------------------------------------------------- the bounds see the mistakes
-@pytest.mark.parametrize("mistake", list(gc.MISTAKES))
-def test_every_planted_mistake_exceeds_the_bounds(mistake):
-    case = CASES[gc.MISTAKES[mistake]]
+@pytest.mark.parametrize("mistake,on", gc.mistake_cases(), ids=[m if (m, on) in gc.MISTAKES.items() else "%s-%s" % (m, on) for m, on in gc.mistake_cases()])
+def test_every_planted_mistake_exceeds_the_bounds(mistake, on):
+    case = CASES[on]
     bd = gc.bounds(case["X"], case["y"], case["a"], case["B"], case["C"], case["sw"])
     assert not gc.violates(gc.reference(case), bd, case["exact_ties"])
-    assert gc.violates(gc.planted(case, mistake), bd, case["exact_ties"]), "%s goes unseen on %s" % (mistake, gc.MISTAKES[mistake])
+    wrong = gc.planted(case, mistake)
+    print("planted %-26s on %-26s: difference / bound %s" % (mistake, on, {k: "%.3g" % v for k, v in gc.ratios(wrong, bd).items()}))
+    assert gc.violates(wrong, bd, case["exact_ties"]), "%s goes unseen on %s" % (mistake, on)
+    if mistake in gc.RANGE_MISTAKES:
+        assert any(v > 1.0 for v in gc.ratios(wrong, bd).values())              # a sum breaks its bound, not a prediction
 
 
 def test_bounds_are_those_the_design_note_quotes():

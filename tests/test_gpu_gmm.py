@@ -64,7 +64,8 @@ def test_step_within_the_bounds(ops, name):
         assert got["ll"] == 0.0 and got["pred"] is None and np.array_equal(got["nk"], bd["ref"]["nk"])
         return
     dec = gc.decided_rows(bd, case["exact_ties"])               # pred_out covers every row, whatever its label
-    assert dec.all() and np.array_equal(got["pred"][dec], bd["ref"]["pred"][dec])
+    assert (~dec).mean() <= case.get("undecided_cap", 0.0)      # 0 below f32mm_plan.LARGE_N rows: no row is excused there
+    assert np.array_equal(got["pred"][dec], bd["ref"]["pred"][dec])
     if "unreached" in case:                                     # no underflowing mass reaches it: exact zeros
         j = case["unreached"]
         assert got["nk"][j] == 0.0 and not got["s1"][j].any() and not got["s2"][j].any()
@@ -79,15 +80,32 @@ def test_bad_labels_equal_the_unlabelled_result(ops):
     assert a["ll"] == b["ll"] and all(np.array_equal(a[q], b[q]) for q in ("nk", "s1", "s2", "pred"))
 
 
-def test_two_calls_return_the_same_bits(ops):
-    case = CASES["four_chains-weights"]
+def test_two_calls_return_the_same_bits(ops, name="four_chains-weights"):
+    case = CASES[name]
     a, b = run(ops, case), run(ops, case)
     assert a["ll"] == b["ll"] and all(np.array_equal(a[q], b[q]) for q in ("nk", "s1", "s2", "pred", "info"))
     assert np.isfinite(a["s2"]).all() and np.abs(a["s1"]).max() > 0
 
 
+@pytest.mark.parametrize("name", ["ranges_x_tiles-weights", "cap32-weights", "colsum_cap-weights"])
+def test_two_calls_return_the_same_bits_over_the_range_plans(ops, name):
+    test_two_calls_return_the_same_bits(ops, name)
+
+
+def test_cached_workspace_holds_no_stale_partials(ops):
+    """One range, then the 32 ranges of cap32 through the same cached workspace, then the one range again: the finish kernel reads the R
+    partials of its own call and nothing a larger call left behind."""
+    small, big = CASES["four_chains-weights"], CASES["cap32-weights"]
+    a = run(ops, small)
+    mid = run(ops, big)
+    b = run(ops, small)
+    assert a["ll"] == b["ll"] and all(np.array_equal(a[q], b[q]) for q in ("nk", "s1", "s2", "pred", "info"))
+    assert np.isfinite(mid["s2"]).all() and np.abs(mid["s1"]).max() > 0
+
+
 @pytest.mark.parametrize("name", ["n1_d1_k1-unlabelled", "k33-mixed", "d768_k100-unlabelled", "full_width-unlabelled", "four_chains-weights",
-                                  "two_ranges-unlabelled", "variance_span", "far_rows", "identical"])
+                                  "two_ranges-unlabelled", "variance_span", "far_rows", "identical", "nt2_phantom-unlabelled",
+                                  "nt2_exact-mixed", "nt8_phantom-unlabelled", "ranges_x_tiles-unlabelled"])
 def test_predict_equals_the_steps_argmax(ops, name):
     case = CASES[name]
     pred, row_ll, resp = ops.gmm_predict(dev(case["X"]), dev(case["a"]), dev(case["B"]), dev(case["C"]), want_ll=True, want_resp=True)

@@ -60,7 +60,8 @@ def test_step_within_the_bounds(ops, name):
         assert got["ll"] == 0.0 and got["pred"] is None and np.array_equal(got["nk"], bd["ref"]["nk"])
         return
     dec = fc.decided_rows(bd, case["exact_ties"])               # pred_out covers every row, whatever its label
-    assert dec.all() and np.array_equal(got["pred"][dec], bd["ref"]["pred"][dec])
+    assert (~dec).mean() <= case.get("undecided_cap", 0.0)      # 0 below f32mm_plan.LARGE_N rows: no row is excused there
+    assert np.array_equal(got["pred"][dec], bd["ref"]["pred"][dec])
     if "unreached" in case:                                     # no underflowing mass reaches it: exact zeros
         j = case["unreached"]
         assert got["nk"][j] == 0.0 and not got["s1c"][j].any() and not got["S"][j].any()
@@ -78,7 +79,8 @@ def test_bad_labels_equal_the_unlabelled_result(ops):
     assert a["ll"] == b["ll"] and all(np.array_equal(a[q], b[q]) for q in ("nk", "s1c", "S", "pred"))
 
 
-@pytest.mark.parametrize("name", ["four_chains-weights", "ranges-mixed", "ragged_j_tile-unlabelled"])
+@pytest.mark.parametrize("name", ["four_chains-weights", "ranges-mixed", "ragged_j_tile-unlabelled", "ranges_x_tiles-weights", "cap32-weights",
+                                  "colsum_cap-weights"])
 def test_two_calls_return_the_same_bits(ops, name):
     case = CASES[name]
     a, b = run(ops, case), run(ops, case)
@@ -86,8 +88,20 @@ def test_two_calls_return_the_same_bits(ops, name):
     assert np.isfinite(a["S"]).all() and np.abs(a["s1c"]).max() > 0
 
 
+def test_cached_workspace_holds_no_stale_partials(ops):
+    """One range, then the 32 ranges of cap32 through the same cached workspace, then the one range again: the finish kernel reads the R
+    partials of its own call and nothing a larger call left behind."""
+    small, big = CASES["jt2_chains-weights"], CASES["cap32-weights"]
+    a = run(ops, small)
+    mid = run(ops, big)
+    b = run(ops, small)
+    assert a["ll"] == b["ll"] and all(np.array_equal(a[q], b[q]) for q in ("nk", "s1c", "S", "pred", "info"))
+    assert np.isfinite(mid["S"]).all() and np.abs(mid["s1c"]).max() > 0
+
+
 @pytest.mark.parametrize("name", ["n1_d1_k1-unlabelled", "one_j_tile-mixed", "ragged_j_tile-unlabelled", "full_width-unlabelled",
-                                  "four_chains-weights", "ranges-unlabelled", "condition_1e4", "far_rows", "identical"])
+                                  "four_chains-weights", "ranges-unlabelled", "condition_1e4", "far_rows", "identical", "jt2_chains-unlabelled",
+                                  "ranges_x_tiles-unlabelled"])
 def test_predict_equals_the_steps_argmax(ops, name):
     case = CASES[name]
     prm = (dev(case["X"]), dev(case["a"]), dev(case["mu"]), dev(case["Ut"]))

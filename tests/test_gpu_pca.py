@@ -46,6 +46,32 @@ def test_gram_and_colsum_within_the_bounds(ops, name):
         assert g[0, 0] == (0.0 if c["a"] is not None else 1.0)
 
 
+@pytest.mark.parametrize("name", ["ranges_x_tiles", "cap32", "colsum_cap"])
+def test_two_calls_return_the_same_bits(ops, name):
+    c = GRAM[pc.gram_name(*pc.NAMED_GRAM[name], True)]
+    x, a = dev(c["X"]), dev(c["a"])
+    (g1, i1), (g2, i2) = ops.pca_gram(x, a), ops.pca_gram(x, a)
+    assert np.array_equal(g1.cpu().numpy(), g2.cpu().numpy()) and np.array_equal(i1.cpu().numpy(), i2.cpu().numpy())
+    assert np.array_equal(ops.pca_colsum(x, a).cpu().numpy(), ops.pca_colsum(x, a).cpu().numpy())
+    assert np.isfinite(g1.cpu().numpy()).all() and np.abs(g1.cpu().numpy()).max() > 0
+
+
+def test_cached_workspace_holds_no_stale_partials(ops):
+    """One range, then the 32 ranges of cap32 through the same cached workspace, then the one range again: the finish kernels read the
+    R and RB partials of their own call and nothing a larger call left behind."""
+    small, big = GRAM[pc.gram_name(3 * pc.T + 5, 129, True)], GRAM[pc.gram_name(*pc.NAMED_GRAM["cap32"], True)]
+
+    def run(c):
+        g, info = ops.pca_gram(dev(c["X"]), dev(c["a"]))
+        return g.cpu().numpy(), info.cpu().numpy(), ops.pca_colsum(dev(c["X"]), dev(c["a"])).cpu().numpy()
+
+    a = run(small)
+    mid = run(big)
+    b = run(small)
+    assert all(np.array_equal(p, q) for p, q in zip(a, b))
+    assert np.isfinite(mid[0]).all() and np.abs(mid[0]).max() > 0
+
+
 def test_a_non_finite_row_is_counted_once(ops):
     c = pc.nan_case()
     g, info = ops.pca_gram(dev(c["X"]), dev(c["a"]))

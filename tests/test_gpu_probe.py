@@ -55,21 +55,38 @@ def test_loss_and_gradient_within_the_bounds(ops, name):
         assert (np.abs(got["gb"] - bd["ref"]["gb"]) <= bd["gb"]).all()
     full = pc.bounds(case["X"], case["y"], case["W"], case["b"], case["sw"])       # pred_out covers every row, whatever its label
     dec = pc.decided_rows(full, case["exact_ties"])
-    assert dec.all()
+    assert (~dec).mean() <= case.get("undecided_cap", 0.0)      # 0 below f32mm_plan.LARGE_N rows: no row is excused there
     assert np.array_equal(got["pred"][dec], full["ref"]["pred"][dec])
     if name == "all_equal":
         assert (got["pred"] == 0).all() and abs(got["loss"] - case["X"].shape[0] * np.log(case["W"].shape[0])) <= bd["loss"]
 
 
-def test_two_calls_return_the_same_bits(ops):
-    case = CASES["four_chains-weights"]
+def test_two_calls_return_the_same_bits(ops, name="four_chains-weights"):
+    case = CASES[name]
     a, b = run(ops, case), run(ops, case)
     assert a["loss"] == b["loss"] and np.array_equal(a["gW"], b["gW"]) and np.array_equal(a["gb"], b["gb"])
     assert np.array_equal(a["pred"], b["pred"]) and np.array_equal(a["info"], b["info"])
     assert np.isfinite(a["gW"]).all() and np.abs(a["gW"]).max() > 0
 
 
-@pytest.mark.parametrize("name", ["n1_d1_c2-base", "c33-base", "d768_c100-no_bias", "full_width-base", "four_chains-base", "large_logit", "ties"])
+@pytest.mark.parametrize("name", ["ranges_x_tiles-weights", "cap32-weights", "colsum_cap-weights"])
+def test_two_calls_return_the_same_bits_over_the_range_plans(ops, name):
+    test_two_calls_return_the_same_bits(ops, name)
+
+
+def test_cached_workspace_holds_no_stale_partials(ops):
+    """One range, then the 32 ranges of cap32 through the same cached workspace, then the one range again: the finish kernels read the R
+    partials of their own call and nothing a larger call left behind."""
+    small, big = CASES["four_chains-weights"], CASES["cap32-weights"]
+    a = run(ops, small)
+    mid = run(ops, big)
+    b = run(ops, small)
+    assert a["loss"] == b["loss"] and all(np.array_equal(a[q], b[q]) for q in ("gW", "gb", "pred", "info"))
+    assert np.isfinite(mid["gW"]).all() and np.abs(mid["gW"]).max() > 0
+
+
+@pytest.mark.parametrize("name", ["n1_d1_c2-base", "c33-base", "d768_c100-no_bias", "full_width-base", "four_chains-base", "large_logit", "ties",
+                                  "nt2_phantom-base", "nt2_exact-base", "nt8_phantom-no_bias", "ranges_x_tiles-base"])
 def test_predict_equals_the_loss_calls_argmax(ops, name):
     case = CASES[name]
     pred, top = ops.probe_predict(dev(case["X"]), dev(case["W"]), dev(case["b"]), want_top=True)

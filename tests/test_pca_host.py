@@ -186,6 +186,7 @@ def test_cases_cover_what_they_claim():
         if c["X"].shape[0] > 1:                                 # (the one-row case is its own mean: c = 0, an exact zero row)
             assert np.isfinite(b).all() and (b <= 1e-2 * np.abs(y).max()).all(), name        # far below any planted mistake
     assert pc.phantom_columns(32) == (96, 32) and pc.phantom_columns(257) == (512 - 288, 288) and pc.phantom_columns(1024) == (0, 1024)
+    assert pc.phantom_columns(129) == (96, 160) and pc.phantom_columns(256) == (0, 256) and pc.phantom_columns(545) == (448, 576)
 
 
 def test_km_cache_is_recovered_by_the_restatement_and_scikit_learn():
@@ -214,9 +215,10 @@ def _fit_inputs(name):
     return X, held, (None if shift0 else pc.rounded_mean(X)), m
 
 
-@pytest.mark.parametrize("mistake", list(pc.MISTAKES))
-def test_planted_mistake_breaks_its_bound(mistake):
-    what, case, kind = pc.MISTAKES[mistake]
+@pytest.mark.parametrize("mistake,case,kind", pc.mistake_cases(),
+                         ids=[m if pc.MISTAKES[m][1] == case else "%s-%s" % (m, case) for m, case, _ in pc.mistake_cases()])
+def test_planted_mistake_breaks_its_bound(mistake, case, kind):
+    what = pc.MISTAKES[mistake][0]
     if kind == "gram":
         c = GRAM[case]
         q = pc.ratio(pc.gram_f64(c["X"], c["a"], mistake), pc.gram_f64(c["X"], c["a"]), pc.gram_bound(c["X"], c["a"]))

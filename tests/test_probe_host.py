@@ -6,6 +6,7 @@ import re
 import numpy as np
 import pytest
 
+import f32mm_plan as fp
 import probe_cases as pc
 
 GIB = 1 << 30
@@ -88,10 +89,12 @@ def test_no_row_is_excused_outside_the_tie_cases(name):
     case = CASES[name]
     bd = pc.bounds(case["X"], case["y"], case["W"], case["b"], case["sw"])
     dec = pc.decided_rows(bd, case["exact_ties"])
+    cap = case.get("undecided_cap", 0.0)                        # 0 below f32mm_plan.LARGE_N rows: no row is excused there
+    assert cap == (fp.UNDECIDED_CAP if case["X"].shape[0] >= fp.LARGE_N else 0.0)
     if name == "ties":
         assert dec.all()                                        # the tied rows are decided exactly, the others by their gap
     else:
-        assert dec.all(), "rows %s have a top-two gap within 2 delta" % np.flatnonzero(~dec)
+        assert (~dec).mean() <= cap, "rows %s have a top-two gap within 2 delta" % np.flatnonzero(~dec)
 
 
 @pytest.mark.parametrize("variant", ["weights", "no_bias", "bad_labels"])
@@ -111,14 +114,17 @@ def test_variants_differ_only_where_they_should(variant):
 
 
 # ------------------------------------------------------------------------------------------------- the bounds see the mistakes
-@pytest.mark.parametrize("mistake", list(pc.MISTAKES))
-def test_every_planted_mistake_exceeds_the_bounds(mistake):
-    case = CASES[pc.MISTAKES[mistake]]
+@pytest.mark.parametrize("mistake,on", pc.mistake_cases(), ids=[m if (m, on) in pc.MISTAKES.items() else "%s-%s" % (m, on) for m, on in pc.mistake_cases()])
+def test_every_planted_mistake_exceeds_the_bounds(mistake, on):
+    case = CASES[on]
     bd = pc.bounds(case["X"], case["y"], case["W"], case["b"], case["sw"])
     clean = pc.loss_grad_f64(case["X"], case["y"], case["W"], case["b"], case["sw"])
     assert not pc.violates(clean, bd, case["exact_ties"])
     wrong = pc.loss_grad_f64(case["X"], case["y"], case["W"], case["b"], case["sw"], mistake=mistake)
-    assert pc.violates(wrong, bd, case["exact_ties"]), "%s goes unseen on %s" % (mistake, pc.MISTAKES[mistake])
+    print("planted %-26s on %-22s: difference / bound %s" % (mistake, on, {k: "%.3g" % v for k, v in pc.ratios(wrong, bd).items()}))
+    assert pc.violates(wrong, bd, case["exact_ties"]), "%s goes unseen on %s" % (mistake, on)
+    if mistake in ("last_range_dropped", "range_added_twice", "range_stride_of_one_tile", "colsum_range_tail_dropped"):
+        assert any(v > 1.0 for v in pc.ratios(wrong, bd).values())              # a sum breaks its bound, not a prediction
 
 
 def test_bounds_leave_little_room():
