@@ -15,6 +15,9 @@ All features, labelled and unlabelled, are L2-normalised once (estimate_k.py:61)
                               by default.  One n x K x d pass per EM step and no n x n pass; K <= 1024, d <= 1024.
                               --covariance_type full | tied fits scd_amd.gmm_full's mixture instead: d <= 64, so with --pca_dim.
 
+--clusterer ward (with acc or silhouette) fits one Ward tree on all rows (scd_amd.ward, docs/design/ward.md) and scores its cut at
+every K a search asks for: no fit per K.  The default, kmeans, is the reference's.
+
 Fits and scores run on the GPU (scd_amd.cluster.KMeans, scd_amd.metrics).  Writes
 ROOT/cluster/estimated_k_{feat_model}_{dataset_name}.json and prints the value to pass as --n_cluster.
 
@@ -48,6 +51,9 @@ def build_parser():
     p.add_argument('--criterion', type=str, default='acc', choices=['acc', 'silhouette', 'bic'],
                    help='acc: clustering accuracy on the labelled rows (GCD); silhouette: mean silhouette coefficient, needs no labels; '
                         'bic: lowest Bayesian information criterion of a diagonal Gaussian mixture, needs no labels')
+    p.add_argument('--clusterer', type=str, default='kmeans', choices=['kmeans', 'ward'],
+                   help='kmeans: one fit per K searched; ward: one Ward tree on all rows (scd_amd.ward), every K is a cut of it; '
+                        'with --criterion acc or silhouette')
     p.add_argument('--covariance_type', type=str, default='diag', choices=['diag', 'spherical', 'full', 'tied'],
                    help="--criterion bic: the mixture's covariances; full and tied (scd_amd.gmm_full) take rows of at most 64 dimensions")
     p.add_argument('--search_mode', type=str, default=None, choices=['brent', 'binary', 'grid', 'finch'],
@@ -63,6 +69,9 @@ def build_parser():
 def parse_args(argv=None):
     """The parsed arguments with the criterion-dependent defaults resolved."""
     args = build_parser().parse_args(argv)
+    if args.clusterer == 'ward' and args.criterion == 'bic':
+        raise SystemExit("--clusterer ward scores cuts of one tree; --criterion bic fits a Gaussian mixture per K and has no use for "
+                         "it: use --criterion acc or silhouette")
     if args.search_mode is None:
         args.search_mode = 'brent' if args.criterion == 'acc' else 'grid'
     if args.min_classes is None and args.criterion in ('silhouette', 'bic'):
@@ -100,8 +109,21 @@ def main(argv=None):
         raise SystemExit(f"--max_classes {big_k} must be above the smallest K searched, {small_k}")
     print(f'{feats.shape[0]} rows, {int(mask_lab.sum())} labelled; searching K in [{small_k}, {big_k}] ({args.search_mode}, {args.criterion})')
     scores = {}
+    tree = None
+    if args.clusterer == 'ward':
+        from scd_amd.ward import ward_tree
+        tree, winfo = ward_tree(feats)
+        print(f"Ward tree: {winfo['rounds']} rounds, {winfo['full_requeries']} full requeries")
 
-    if sil:
+    if tree is not None:
+        targets_dev = None if sil else torch.as_tensor(targets, device=dev)
+        mask_dev = None if sil else torch.as_tensor(mask_lab, device=dev)
+
+        def evaluate(K):
+            s, scores[int(K)] = ek.evaluate_cut(K, feats, tree, targets_dev, mask_dev, verbose=True)
+            return s
+        name = 'silhouette' if sil else 'labelled_acc'
+    elif sil:
         def evaluate(K):
             s, scores[int(K)] = ek.evaluate_k_unlabelled(K, feats, verbose=True)
             return s
@@ -137,7 +159,7 @@ def main(argv=None):
     else:
         k, trace = ek.grid_search(evaluate, small_k, big_k, log=print)
         out = dict(trace=[dict(ks=list(ks), scores=list(sc), best=int(b)) for ks, sc, b in trace])
-    out.update(k=int(k), criterion=args.criterion, search_mode=args.search_mode, min_classes=int(small_k), max_classes=int(big_k),
+    out.update(k=int(k), criterion=args.criterion, clusterer=args.clusterer, search_mode=args.search_mode, min_classes=int(small_k), max_classes=int(big_k),
                scores={str(kk): v for kk, v in sorted(scores.items())})
     if args.pca_dim:
         out.update(pca_dim=int(args.pca_dim), pca_whiten=bool(args.pca_whiten))

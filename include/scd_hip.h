@@ -480,6 +480,33 @@ int scd_mr_nearest(scd_handle h, const float* U, int64_t n, int d, const double*
 int scd_hdbscan_tree(const int32_t* lo, const int32_t* hi, const double* weight, int64_t n, int min_cluster_size, int method,
                      int allow_single_cluster, int32_t* labels_out, double* prob_out, int32_t* n_clusters_out);
 
+/* ---- Ward agglomerative clustering (no counterpart in the reference; scipy's linkage(x, 'ward') and scikit-learn's
+ *      AgglomerativeClustering(linkage='ward'); docs/design/ward.md) ---- */
+/* The nearest-neighbour search of one round of the reciprocal-pair procedure, without the n x n matrix.  The table is X float32 [m, d]
+ * (centroids) with xcnt int32 [m] (sizes); a position of size 0 is dead.  Query p is the row Q_p of Q float32 [q, d] with size qcnt[p]
+ * >= 1 and qself[p], the column that is the query itself, or -1.  With qn = the float64 dot of a row with itself and v_pj the float64
+ * dot of Q_p and X_j (scd_knn's), D = max(0, (qn_p + qn_j) - 2 v_pj), w = ((double)a * (double)b) / (double)(a + b) for a = qcnt[p],
+ * b = xcnt[j], cost_pj = w * D, every operation in double and rounded once:
+ * nn_out[p] = the live column j != qself[p] of the least cost_pj, ties to the lowest j; cost_out[p] = that cost (double; the height of
+ * the merge is sqrt(2 cost)); a query without a live foreign column gets -1 and +inf.  info_out int32 [4] as scd_knn's.  Two fp16 MFMA
+ * passes with an error bound computed from the rows propose candidates, float64 decides; the result never depends on them; two calls
+ * return the same bits.
+ * prepared: the workspace still holds the fp16 copy, row statistics and norms of positions 0 .. prepared - 1 of this X (same m and d)
+ * from earlier calls, kept up to date by scd_ward_merge; 0 prepares everything, m nothing.  Limits: 1 <= q < 2^29, 2 <= m < 2^29, d
+ * rounded up to 32 <= 1024; scd_ward_nearest_ws_bytes returns 0 outside them.  The workspace holds the fp16 copies of X and Q and
+ * scd_knn_slots() int32 slots per query: 0.68 GB at q = m = 126,976, d = 768. */
+size_t scd_ward_nearest_ws_bytes(int64_t q, int64_t m, int d);
+int scd_ward_nearest(scd_handle h, const float* Q, const int32_t* qcnt, const int32_t* qself, const float* X, const int32_t* xcnt, int64_t q,
+                     int64_t m, int d, int64_t prepared, int32_t* nn_out, double* cost_out, int32_t* info_out, void* ws, size_t ws_bytes,
+                     void* stream);
+/* The merges of one round, in place: for each of the `pairs` pairs (lo[e], hi[e]), lo < hi, both live, no position in two pairs:
+ * X_lo <- fl32(((double)a X_lo + (double)b X_hi) / (double)(a + b)) per coordinate with a = xcnt[lo], b = xcnt[hi] (the products are
+ * exact below 2^29 rows), xcnt[lo] = a + b, xcnt[hi] = 0, and the prepared data of position lo in the workspace of scd_ward_nearest
+ * (any q; the table's part depends on m and d alone) is made again.  A pair that breaks the conditions is left alone.  With the two
+ * entries a C host drives a whole fit: search the stale clusters, merge the reciprocal pairs, repeat. */
+int scd_ward_merge(scd_handle h, float* X, int32_t* xcnt, const int32_t* lo, const int32_t* hi, int64_t pairs, int64_t m, int d, void* ws,
+                   size_t ws_bytes, void* stream);
+
 /* ---- the linear probe: multinomial logistic regression on frozen features (the linear evaluation of DINO / DINOv2; scikit-learn's
  *      LogisticRegression(C) written as a sum; the reference trains the same head in gcd/methods/cluster_and_classifier/
  *      train_supervised.py; docs/design/probe.md) ---- */

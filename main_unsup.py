@@ -7,7 +7,7 @@ Here every stage starts from the reference's own cache files under --root_dir, b
   extracted_features/{feat_model}_{dataset}_all.pt   dict all_feats, mask_lab, mask_cls, targets      (:141-146,294-301)
   extracted_features/clip_{dataset}_all.pt           same dict, CLIP features                          (:306-311)
   cluster/{cluster}_{feat_model}_{dataset}_{n_cluster}.pt   dict all_preds, u_preds, u_targets, mask  (:366-374)
-                                                            ({cluster} = KM, SSKM, ConSSKM, FINCH, SC or GMM)
+                                                            ({cluster} = KM, SSKM, ConSSKM, FINCH, SC, GMM or WARD; WARD adds linkage)
   cluster/HDBSCAN_{feat_model}_{dataset}_mcs{min_cluster_size}[_ms{min_samples}].pt   the same dict plus noise, probabilities, n_cluster
                                                             (--cluster HDBSCAN: the number of clusters is a result, not a flag)
   zeroshot_weights/zeroshot_weights_all_{nouns|wikibird|wikidog}_vit_b_16.pt   tensor [512, V]        (:389-394)
@@ -66,6 +66,8 @@ def build_parser():
     p.add_argument('--cluster', type=str, default='KM', help='options: KM, SSKM, ConSSKM, FINCH (first-neighbour clustering refined to --n_cluster clusters), '
                                                                      'SC (spectral clustering on the exact k-NN graph, see --n_neighbors), '
                                                                      'HDBSCAN (no --n_cluster: the number of clusters is a result, see --min_cluster_size), '
+                                                                     'WARD (agglomerative clustering with Ward linkage cut at --n_cluster; the whole tree '
+                                                                     'is stored as linkage, so another K needs no refit), '
                                                                      'GMM (a diagonal Gaussian mixture of --n_cluster components, see --covariance_type), '
                                                                      'GMM_FULL, GMM_TIED (a covariance matrix per component, or one for all; rows of at '
                                                                      'most 64 dimensions, see --pca_dim; --covariance_type is not read)')
@@ -180,6 +182,8 @@ def run_clustering(args, u_feats, l_feats, l_targets, semi_supervised=False):
         from scd_amd.spectral import SpectralClustering
         sc = SpectralClustering(n_clusters=args.n_cluster, n_neighbors=args.n_neighbors, random_state=0)
         return None, sc.fit_predict(np.asarray(u_feats, dtype=np.float32)).astype(np.int64)
+    elif args.cluster == 'WARD':
+        return None, run_ward(args, u_feats)['u_preds']
     elif args.cluster == 'GMM' or args.cluster in FULL_COVARIANCE:
         return run_gmm(args, u_feats, l_feats, l_targets) if semi_supervised else run_gmm(args, u_feats)
     else:
@@ -188,6 +192,16 @@ def run_clustering(args, u_feats, l_feats, l_targets, semi_supervised=False):
     km.fit_mix(u.float(), l.float(), lt)
     all_preds = km.labels_.cpu().numpy()
     return all_preds, all_preds[len(l_targets):]
+
+
+def run_ward(args, u_feats):
+    """--cluster WARD on the unlabelled rows (docs/design/ward.md): scikit-learn's AgglomerativeClustering(n_clusters, linkage='ward').
+    One fit gives the whole tree; the labels are its cut at n_cluster.  Returns the entries of the result file: u_preds and linkage
+    (scipy's Z: scd_amd.ward.cut_tree(linkage, K) gives the labels at any other K without a refit)."""
+    from scd_amd.ward import Ward
+    w = Ward(n_clusters=args.n_cluster).fit(np.asarray(u_feats, dtype=np.float32))
+    print(f"WARD: {w.info_['rounds']} rounds, {w.info_['full_requeries']} full requeries, {w.info_['inversions']} inversions")
+    return dict(u_preds=w.labels_, linkage=w.linkage_)
 
 
 def run_hdbscan(args, u_feats):
@@ -359,6 +373,8 @@ def main(argv=None):
         u_feats, l_feats = pca_reduce(args, u_feats, l_feats)
         if args.cluster == 'HDBSCAN':
             cluster_result = dict(all_preds=None, u_targets=u_targets, mask=mask, **run_hdbscan(args, u_feats))
+        elif args.cluster == 'WARD':
+            cluster_result = dict(all_preds=None, u_targets=u_targets, mask=mask, **run_ward(args, u_feats))
         else:
             all_preds, preds = run_clustering(args, u_feats, l_feats, l_targets)
             cluster_result = dict(all_preds=all_preds, u_preds=preds, u_targets=u_targets, mask=mask)

@@ -195,6 +195,11 @@ SIGNATURES = {
     "scd_mr_nearest": (_i, [_vp, _vp, _i64, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     # lo, hi, weight, n, min_cluster_size, method, allow_single_cluster, labels_out, prob_out, n_clusters_out
     "scd_hdbscan_tree": (_i, [_vp, _vp, _vp, _i64, _i, _i, _i, _vp, _vp, C.POINTER(C.c_int32)]),
+    "scd_ward_nearest_ws_bytes": (_sz, [_i64, _i64, _i]),
+    # h, Q, qcnt, qself, X, xcnt, q, m, d, prepared, nn_out, cost_out, info_out, ws, ws_bytes, stream
+    "scd_ward_nearest": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i, _i64, _vp, _vp, _vp, _vp, _sz, _vp]),
+    # h, X, xcnt, lo, hi, pairs, m, d, ws, ws_bytes, stream
+    "scd_ward_merge": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i, _vp, _sz, _vp]),
     "scd_munkres": (_i, [_vp, _i, _i, _vp, C.POINTER(_i)]),
     "scd_munkres_sparse": (_i, [_i, _i64, _vp, _vp, _vp, _vp, C.POINTER(_i)]),
     "scd_transport_solve": (_i, [_vp, _i64, _i, _i, _i, _vp, C.POINTER(_i64)]),

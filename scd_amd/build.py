@@ -16,7 +16,7 @@ LIB = os.path.join(LIBDIR, "libscd_hip.so")
 OBJDIR = os.path.join(LIBDIR, "obj")
 
 SOURCES = ["api.cpp", "munkres.cpp", "munkres_sparse.cpp", "transport.cpp", "hdbscan_tree.cpp", "comm.cpp", "kmeans.hip", "mstep.hip", "sim.hip", "vote.hip", "gemm.hip",
-           "encoder.hip", "image.hip", "jpeg.hip", "metrics.hip", "silhouette.hip", "finch.hip", "knn.hip", "tsne.hip", "probe.hip", "graph.hip", "hdbscan.hip", "gmm.hip", "pca.hip", "gmm_full.hip"]
+           "encoder.hip", "image.hip", "jpeg.hip", "metrics.hip", "silhouette.hip", "finch.hip", "knn.hip", "tsne.hip", "probe.hip", "graph.hip", "hdbscan.hip", "gmm.hip", "pca.hip", "gmm_full.hip", "ward.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-atomics", "-Wno-unused-result",
          "-fno-gpu-rdc"]

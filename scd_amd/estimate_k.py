@@ -12,6 +12,7 @@ Without labelled rows (main_unsup.py's setting) there is nothing to take an accu
   * `grid_search`           is an integer search for it - bounded Brent on an integer-truncated K is fragile for this criterion
                             (docs/design/estimate_k.md, "Without labels").
 
+  * `evaluate_cut`          scores the cut at K of a Ward tree fitted once (scd_amd.ward; docs/design/ward.md): no fit per K;
   * `finch_search`          scores only the cluster counts FINCH's partitions propose (scd_amd.finch; docs/design/finch.md): a
                             handful of fits instead of a sweep.
 
@@ -76,6 +77,27 @@ def evaluate_k_bic(K, feats, covariance_type="diag", verbose=False, **gmm_kw):
     if verbose:
         print('K = {}: BIC {:.1f}, lower bound {:.6f} ({} iterations)'.format(K, bic, gm.lower_bound_, gm.n_iter_))
     return -bic, {'bic': bic, 'lower_bound': float(gm.lower_bound_), 'n_iter': int(gm.n_iter_), 'converged': bool(gm.converged_)}
+
+
+def evaluate_cut(K, feats, Z, targets=None, mask_lab=None, verbose=False):
+    """One K of the search on a Ward tree fitted once (scd_amd.ward.ward_tree's Z on all rows of feats): the labels are the tree's cut at
+    K, no fit.  With targets and mask_lab the score is evaluate_k's (labelled ACC, the score dict); without them evaluate_k_unlabelled's
+    (silhouette, {'silhouette': s})."""
+    import torch
+    from .ward import cut_tree
+    K = int(K)
+    labels = torch.as_tensor(cut_tree(Z, K).astype(np.int32), device=feats.device)
+    if targets is None:
+        s = metrics.silhouette_score(feats, labels)
+        if verbose:
+            print('K = {}: silhouette {:.4f}'.format(K, s))
+        return s, {'silhouette': s}
+    scores = metrics.score_split(labels, targets, mask_lab)
+    if scores["labelled"] is None:
+        raise ValueError("mask_lab selects no row: the estimator scores K on the labelled rows")
+    if verbose:
+        print('K = {}: labelled acc {:.4f}'.format(K, scores["labelled"]["acc"]))
+    return scores["labelled"]["acc"], scores
 
 
 class _Memo:

@@ -1033,6 +1033,61 @@ def mr_nearest(u, core, comp, ws=None, prepared=False):
     return nn, r, info
 
 
+# ----------------------------------------------------------------------------- Ward primitives (docs/design/ward.md)
+WARD_WS_CAP = 2 << 30           # a fit's workspace stays under 2 GiB: 126,976 x 768 needs 0.68 GB
+
+
+def ward_workspace(q, m, d, device):
+    """The workspace of `ward_nearest` for up to q queries against a table of m positions of d columns: allocate once per fit; the table's
+    part (the fp16 copy, row statistics and norms) is kept between calls and refreshed by `ward_merge`."""
+    nb = _L().scd_ward_nearest_ws_bytes(int(q), int(m), int(d))
+    if nb == 0:
+        raise _lib.ScdError(_lib.SCD_EINVAL, "ward_nearest: q = %d, m = %d, d = %d outside the limits 1 <= q < 2^29, 2 <= m < 2^29, d <= 1024"
+                            % (q, m, d))
+    if nb > WARD_WS_CAP:
+        raise _lib.ScdError(_lib.SCD_EINVAL, "ward_nearest: the workspace for q = %d, m = %d, d = %d is %d bytes, over the 2 GiB cap"
+                            % (q, m, d, nb))
+    return _ws(nb, device)
+
+
+def ward_nearest(q, qcnt, qself, x, xcnt, ws=None, prepared=0):
+    """scd_ward_nearest: queries q float32 [nq, d] with sizes qcnt int32 [nq] and own columns qself int32 [nq] (-1: none) against the
+    table x float32 [m, d] with sizes xcnt int32 [m] (0: dead), all on the device -> (nn int32 [nq], cost float64 [nq], info int32 [4]).
+    nn[p] = the live column j != qself[p] of the least Ward cost, ties to the lowest j; -1 and +inf for a query without one.
+    ws: `ward_workspace(nq, m, d, device)` or larger in q; prepared: how many leading positions of x it still holds."""
+    _need_cuda(q, qcnt, qself, x, xcnt)
+    if q.dim() != 2 or x.dim() != 2 or q.dtype != torch.float32 or x.dtype != torch.float32 or q.shape[1] != x.shape[1] \
+            or qcnt.dtype != torch.int32 or qself.dtype != torch.int32 or xcnt.dtype != torch.int32 \
+            or qcnt.shape != (q.shape[0],) or qself.shape != (q.shape[0],) or xcnt.shape != (x.shape[0],):
+        raise _lib.ScdError(_lib.SCD_EINVAL, "ward_nearest: q float32 [nq, d], qcnt, qself int32 [nq], x float32 [m, d], xcnt int32 [m]")
+    if not x.is_contiguous() or not xcnt.is_contiguous():
+        raise _lib.ScdError(_lib.SCD_EINVAL, "ward_nearest: x and xcnt must be contiguous (the workspace's copy belongs to this table)")
+    q, qcnt, qself = q.contiguous(), qcnt.contiguous(), qself.contiguous()
+    (nq, d), m = q.shape, x.shape[0]
+    if ws is None:
+        ws, prepared = ward_workspace(nq, m, d, x.device), 0
+    nn = torch.empty(nq, dtype=torch.int32, device=x.device)
+    cost = torch.empty(nq, dtype=torch.float64, device=x.device)
+    info = torch.empty(4, dtype=torch.int32, device=x.device)
+    check(_L().scd_ward_nearest(handle(), ptr(q), ptr(qcnt), ptr(qself), ptr(x), ptr(xcnt), nq, m, d, int(prepared), ptr(nn), ptr(cost),
+                                ptr(info), ptr(ws), ws.numel(), stream_ptr()))
+    return nn, cost, info
+
+
+def ward_merge(x, xcnt, lo, hi, ws):
+    """scd_ward_merge, in place: the pairs (lo[e], hi[e]) int32 of one round, lo < hi, no position twice.  x[lo] becomes the weighted
+    centroid, xcnt[lo] the sum, xcnt[hi] = 0, and the workspace's data of position lo is made again."""
+    _need_cuda(x, xcnt, lo, hi, ws)
+    if x.dim() != 2 or x.dtype != torch.float32 or xcnt.dtype != torch.int32 or xcnt.shape != (x.shape[0],) or lo.dtype != torch.int32 \
+            or hi.dtype != torch.int32 or lo.dim() != 1 or lo.shape != hi.shape:
+        raise _lib.ScdError(_lib.SCD_EINVAL, "ward_merge: x float32 [m, d], xcnt int32 [m], lo and hi int32 [pairs]")
+    if not (x.is_contiguous() and xcnt.is_contiguous()):
+        raise _lib.ScdError(_lib.SCD_EINVAL, "ward_merge: x and xcnt are changed in place and must be contiguous")
+    lo, hi = lo.contiguous(), hi.contiguous()
+    check(_L().scd_ward_merge(handle(), ptr(x), ptr(xcnt), ptr(lo), ptr(hi), lo.numel(), x.shape[0], x.shape[1], ptr(ws), ws.numel(),
+                              stream_ptr()))
+
+
 HDBSCAN_METHODS = {"eom": 0, "leaf": 1}
 
 
