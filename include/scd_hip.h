@@ -396,8 +396,12 @@ int scd_contingency_stats(scd_handle h, const int32_t* table, int s, int kp, int
  * 2 dot) with the fp32 norms of the fp16 rows, the pair i = j excluded by index, per-cluster sums in fp32, the mean in float64 over a
  * fixed partition and tree.  No floating-point atomics: two calls on one input return the same bits.
  * Limits: 2 <= n <= 2^30, 1 <= d <= 1024, 2 <= k <= n; scd_silhouette_ws_bytes returns 0 outside them.  The workspace holds the
- * label-sorted fp16 copy of X: about 2 n (d rounded up to 64) bytes. */
+ * label-sorted fp16 copy of X: about 2 n (d rounded up to 64) bytes.
+ * scd_silhouette_ranges: the number of cluster ranges (grid.y, 1 ... 32) scd_silhouette launches with for n rows and k ids on this
+ * handle's device: min(k, 32, ceil(4 CUs / ceil(n / 128))).  Read-only; the samples do not depend on it.  0 for a null handle or
+ * n, k outside the limits. */
 size_t scd_silhouette_ws_bytes(int64_t n, int d, int k);
+int scd_silhouette_ranges(scd_handle h, int64_t n, int k);
 int scd_silhouette(scd_handle h, const void* X, int x_dtype, const int32_t* labels, int64_t n, int d, int k, float* samples_out,
                    double* mean_out, int64_t* info_out, void* ws, size_t ws_bytes, void* stream);
 

@@ -128,6 +128,7 @@ SIGNATURES = {
     # h, table, s, kp, kt, ints_out, info_out, ws, ws_bytes, stream
     "scd_contingency_stats": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     "scd_silhouette_ws_bytes": (_sz, [_i64, _i, _i]),
+    "scd_silhouette_ranges": (_i, [_vp, _i64, _i]),
     # h, X, x_dtype, labels, n, d, k, samples_out, mean_out, info_out, ws, ws_bytes, stream
     "scd_silhouette": (_i, [_vp, _vp, _i, _vp, _i64, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "scd_first_neighbor_ws_bytes": (_sz, [_i64, _i]),

@@ -410,6 +410,22 @@ extern "C" size_t scd_silhouette_ws_bytes(int64_t n, int d, int k) {
     return p.end;
 }
 
+// ranges of clusters (grid.y of sl_main_kernel): enough blocks to fill the device a few times over when there are few panels.  The
+// result does not depend on it: a row's a-sum comes from one block, and the minimum over the ranges is exact.
+static int sl_ranges(int n_cu, int64_t n, int k) {
+    const long long panels = scd_cdiv(n, SL_BM);
+    long long ny = scd_cdiv(4ll * n_cu, panels);
+    const int ny_max = k < SL_YMAX ? k : SL_YMAX;
+    if (ny > ny_max) ny = ny_max;
+    if (ny < 1) ny = 1;
+    return (int)ny;
+}
+
+extern "C" int scd_silhouette_ranges(scd_handle h, int64_t n, int k) {
+    if (!h || !sl_shape_ok(n, 1, k)) return 0;
+    return sl_ranges(h->n_cu, n, k);
+}
+
 extern "C" int scd_silhouette(scd_handle h, const void* X, int x_dtype, const int32_t* labels, int64_t n, int d, int k, float* samples_out,
                               double* mean_out, int64_t* info_out, void* ws, size_t ws_bytes, void* stream_) {
     SCD_DEVICE_ENTRY(h, "scd_silhouette");
@@ -449,12 +465,8 @@ extern "C" int scd_silhouette(scd_handle h, const void* X, int x_dtype, const in
         sl_gather_kernel<half_t><<<(unsigned)gather_blocks, 256, 0, st>>>((const half_t*)X, labels, n, d, p.ld, p.chunks, p.n_alloc, hist, meta,
                                                                          rowpos, Xs, nrm, slab);
     SCD_LAUNCH_CHECK();
-    // ranges of clusters (grid.y): enough blocks to fill the device a few times over when there are few panels.  The result does not
-    // depend on it: a row's a-sum comes from one block, and the minimum over the ranges is exact.
     const long long panels = scd_cdiv(n, SL_BM);
-    long long ny = scd_cdiv(4ll * h->n_cu, panels);
-    if (ny > p.ny_max) ny = p.ny_max;
-    if (ny < 1) ny = 1;
+    const int ny = sl_ranges(h->n_cu, n, k);                    // <= p.ny_max, which sizes part_b
     { const int rc_ = scd_set_max_lds((const void*)sl_main_kernel, SL_LDS_BYTES); if (rc_) return rc_; }
     sl_main_kernel<<<dim3((unsigned)panels, (unsigned)ny), SL_THREADS, SL_LDS_BYTES, st>>>(Xs, nrm, slab, off, meta, k, p.ld, p.dp, p.n_alloc,
                                                                                           a_sum, part_b);

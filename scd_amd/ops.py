@@ -896,6 +896,12 @@ def silhouette(x, labels, k):
     return samples, mean, info
 
 
+def silhouette_ranges(n, k):
+    """scd_silhouette_ranges: the number of cluster ranges (grid.y) silhouette() launches with for n rows and k ids on this device
+    (0 outside the kernel's limits).  The samples do not depend on it; tests size their cases with it."""
+    return int(_L().scd_silhouette_ranges(handle(), int(n), int(k)))
+
+
 # ----------------------------------------------------------------------------- FINCH primitives (docs/design/finch.md)
 def first_neighbor(u):
     """scd_first_neighbor: u float32 [n, d] on the device -> (nn int32 [n], d1 float64 [n], info int32 [2] = rows through the exact
